@@ -12,10 +12,14 @@ per GPU, each owns a contiguous APPLE cell range of its own 10M cells (decomp_de
 weak scaling); the one cross-rank exchange is the all-reduce of the atmosphere cells shared
 by neighbouring ranks (libfcx's RCCL communicator), once per step.
 
-Also reported:
+A plain run sets the workload up, warms up, times --steps steps, writes the outputs of the
+last one if --dump-outputs names a folder, and prints the result line.  It also reports
   roofline      algorithmic bytes of the step's one launch (fcx_run_group) / its mean device
                 time per timed step (one HIP event pair around the timed steps; --group 0: an
                 event pair per step around the dominant engine's launch)
+With --full the line also holds the cold step, each variant's own kernel time (kernels),
+multi_gpu_check, the same workload on the other atmosphere map (other_map), in fp32
+(config5_fp32) and on config 4's fixed grid (config4), the end-to-end host-array rates (e2e) and
   cpu_baseline  the reference path on this box's host cores (rank 0, N=1 only; cpu_legs.py):
                 the reference flux_lib compiled from source (oracle/_ref, kind "reference";
                 the C restatement oracle/fco.c, kind "port", where it was not built) on one
@@ -42,14 +46,27 @@ VARIANTS = ("CCLM", "MOM5", "RCO")
 MIN_WARMUP_S = 0.15  # back-to-back device work before the timed steps, whatever --warmup says
 WARMUP_BLOCK = 10    # warm-up steps between two synchronisations
 COLD_IDLE_S = 0.5    # idle gap before the cold step
+DUMP_SAMPLE = 131072  # --dump-outputs: cells written of an array that holds more
+DUMP_BYTES = 60e6     # --dump-outputs: all files together stay below this (the sample shrinks)
+DUMP_SEED = 20231015  # --dump-outputs: seed of the sampled cells (with the array's length)
 
 
 def parse():
     p = argparse.ArgumentParser()
     p.add_argument("--gpus", type=int, default=1,
                    help="ranks (one per GPU); without a launcher bench.py starts torch.distributed.run itself")
-    p.add_argument("--steps", type=int, default=200)
+    p.add_argument("--steps", type=int, default=200, help="timed steps (exactly this many)")
     p.add_argument("--warmup", type=int, default=200)
+    p.add_argument("--full", action="store_true",
+                   help="everything beside the headline figure as well: the cold step, per-variant kernel "
+                        "times, multi_gpu_check, the all-reduce alone, the other atmosphere map, config 5's "
+                        "fp32 kernels, config 4, the end-to-end host-array rates and the CPU baselines "
+                        "(each with its own switch below); without it only the main workload is set up, "
+                        "warmed up and timed")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step left in the caller's output "
+                        "arrays (every variant's fluxes and atmosphere fields; arrays above DUMP_SAMPLE "
+                        "cells as a fixed seeded sample of cells) to DIR/<name>.npy")
     p.add_argument("--cells", type=int, default=10_000_000, help="exchange-grid cells per GPU (weak scaling)")
     p.add_argument("--global-cells", type=int, default=0,
                    help="fixed global grid sharded over the ranks by APPLE ranges (strong scaling, "
@@ -58,10 +75,10 @@ def parse():
     p.add_argument("--types", type=int, default=1, help="surface types")
     p.add_argument("--bias", action="store_true", help="monthly evaporation bias corrections")
     p.add_argument("--cpu-seconds", type=float, default=3.0,
-                   help="CPU baselines: seconds per leg (1 core and all cores, at 32,768 cells and --cells)")
+                   help="--full: CPU baselines, seconds per leg (1 core and all cores, at 32,768 cells and --cells)")
     p.add_argument("--no-cpu", action="store_true")
     p.add_argument("--e2e", type=int, default=1,
-                   help="N=1: also time the end-to-end host-array step at 10M and 32,768 cells (an 'e2e' "
+                   help="--full, N=1: also time the end-to-end host-array step at 10M and 32,768 cells (an 'e2e' "
                         "sub-object; never the `value`)")
     p.add_argument("--atmos", type=int, default=1,
                    help="exchange->atmosphere accumulation (+ one RCCL all-reduce when N>1)")
@@ -70,10 +87,10 @@ def parse():
                    help="N > 1: the boundary all-reduce through libfcx's RCCL communicator (default) or "
                         "torch.distributed (rehearsals)")
     p.add_argument("--config5", type=int, default=1,
-                   help="N = 1, fp64 line: also time the fp32 variant of the same workload (BASELINE config 5's "
+                   help="--full, N = 1, fp64 line: also time the fp32 variant of the same workload (BASELINE config 5's "
                         "fp32 kernels, a 'config5_fp32' sub-object; never the `value`)")
     p.add_argument("--config4", type=int, default=40_000_000,
-                   help="also time config 4's fixed grid of this many cells sharded over the ranks "
+                   help="--full: also time config 4's fixed grid of this many cells sharded over the ranks "
                         "(strong scaling, a 'config4' sub-object); 0 = off")
     p.add_argument("--same-device", action="store_true",
                    help="rehearsal only: every rank on GPU 0 (with --backend gloo on a 1-GPU box)")
@@ -84,7 +101,7 @@ def parse():
                         "the kernel's 128-cell wave tiles, as on a real intersection grid), or periodic runs "
                         "of 3,4,5,4 cells (no segment crosses a tile; the round-1 bench map)")
     p.add_argument("--other-map", type=int, default=1,
-                   help="also time the same workload on the other atmosphere map (an 'other_map' sub-object)")
+                   help="--full: also time the same workload on the other atmosphere map (an 'other_map' sub-object)")
     p.add_argument("--caller-device", action="store_true",
                    help="bind the caller's device arrays (contiguous torch tensors, the inputs shared "
                         "by the variants) instead of host arrays whose engine-owned device mirrors "
@@ -439,6 +456,46 @@ def link_bytes(variants, n, args):
     return b_in, b_out
 
 
+def dump_outputs(wl, folder, rank, world):
+    """--dump-outputs: the arrays a caller of the timed path holds after its last step, as
+    folder/<variant>.flux.s<type>.g<grid>.<NAME>.npy (the case's output fields) and
+    folder/<variant>.atmos.<NAME>.npy (the accumulated atmosphere fields), in their own
+    float32 / float64 (N > 1: every rank its own files, rank<r>.<...>).  Host-bound workloads
+    download the engines' device outputs into the host arrays first, as a caller would.  An
+    array of more than `per` cells is written as a sample: the sorted distinct cells drawn by
+    a generator seeded with (DUMP_SEED, the array's length), the same in every run with the
+    same arguments; `per` is DUMP_SAMPLE, or less where the files would pass DUMP_BYTES."""
+    import torch
+    from fcx.workload import ATM_FIELDS
+
+    os.makedirs(folder, exist_ok=True)
+    torch.cuda.synchronize()
+    if not wl.caller_device:
+        wl.download()
+    arrays = []
+    for v, case in zip(wl.variants, wl.cases):
+        arrays += [(f"{v}.flux.s{s}.g{g}.{name}", case.lf.field[(s, g, name)])
+                   for s, g, name in dict.fromkeys(case.outputs)]
+    if wl.la is not None:
+        for v, outs in zip(wl.variants, wl.atm_outs):
+            arrays += [(f"{v}.atmos.{name}", outs[name][:wl.la.n_atmos]) for name, _ in ATM_FIELDS]
+    per = max(1, min(DUMP_SAMPLE, int(DUMP_BYTES // (8 * max(len(arrays), 1)))))
+    picks = {}
+    prefix = f"rank{rank}." if world > 1 else ""
+    for name, a in arrays:
+        n = int(a.shape[0])
+        if n > per:
+            if n not in picks:
+                picks[n] = np.unique(np.random.default_rng([DUMP_SEED, n]).integers(0, n, per))
+            a = a[torch.as_tensor(picks[n], device=a.device)] if isinstance(a, torch.Tensor) else a[picks[n]]
+        if isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        a = np.ascontiguousarray(a)
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        np.save(os.path.join(folder, prefix + name + ".npy"), a)
+
+
 def relaunch(n):
     """`python bench.py --gpus N` outside a launcher: run this same command under
     torch.distributed.run (one rank per GPU, rendezvous on 127.0.0.1) as a child process,
@@ -454,15 +511,19 @@ def relaunch(n):
     return subprocess.call(cmd)
 
 
-def measure(wl, args, world, dist, comm, steps, warmup, t_base=0, cold=False):
+def measure(wl, args, world, dist, comm, steps, warmup, t_base=0, cold=False, probe=True):
     """Warm-up (at least `warmup` steps and MIN_WARMUP_S of device work), then EXACTLY
     `steps` timed steps bracketed by barrier + synchronize, max over ranks.  A step is
     fcx_run of every variant's engine plus, for N > 1, the ONE all-reduce of the boundary
-    slots of all variants (libfcx's RCCL communicator) and their finish."""
+    slots of all variants (libfcx's RCCL communicator) and their finish.
+    probe: the event-timed warm-up block of every engine's own launch (the per-variant kernel
+    times; it also picks the dominant engine, which the per-engine step needs for its events,
+    so only the grouped step can go without it)."""
     import torch
 
     stream = wl.stream
     group = bool(args.group)
+    probe = probe or not group
 
     def step(t, events=None, grouped=group):
         if grouped:  # fcx_run_group: the variants' flux passes as one launch
@@ -480,7 +541,7 @@ def measure(wl, args, world, dist, comm, steps, warmup, t_base=0, cold=False):
     # event-timed warm-up block: every engine's launch, to pick the dominant one (and report
     # the others); the timed steps then carry ONE event pair, around the dominant launch --
     # each pair in the step costs ~2.5 % of it (bench/event_probe.py)
-    probe_steps = max(WARMUP_BLOCK, min(steps, 200))
+    probe_steps = max(WARMUP_BLOCK, min(steps, 200)) if probe else 0
     ev_probe = pairs(probe_steps)
     # the timed steps' events exist before the warm-up starts: nothing host-side sits between
     # the warm-up and the timed region (an idle GPU drops its clocks)
@@ -524,17 +585,19 @@ def measure(wl, args, world, dist, comm, steps, warmup, t_base=0, cold=False):
         torch.cuda.synchronize()
         if all_ranks(warm >= warmup and time.perf_counter() - t_w >= MIN_WARMUP_S):
             break
-    for k in range(probe_steps):  # still warm-up: the event-timed block, one launch per engine
-        step(t_base + (warm + k) * 3600, ev_probe[k], grouped=False)
-    torch.cuda.synchronize()
-    probe_ms = np.array([[a.elapsed_time(b) for (a, b) in row] for row in ev_probe])  # [steps][variant]
-    dom = int(np.argmax(probe_ms.mean(axis=0)))
-    if args.kernel_events == "dominant":
-        ev = [[p if i == dom else None for i, p in enumerate(row)] for row in ev]
-    for k in range(WARMUP_BLOCK):  # back under load after the host read the probe events
-        step(t_base + (warm + probe_steps + k) * 3600)
-    torch.cuda.synchronize()
-    warm += probe_steps + WARMUP_BLOCK
+    probe_ms, dom = None, None
+    if probe:
+        for k in range(probe_steps):  # still warm-up: the event-timed block, one launch per engine
+            step(t_base + (warm + k) * 3600, ev_probe[k], grouped=False)
+        torch.cuda.synchronize()
+        probe_ms = np.array([[a.elapsed_time(b) for (a, b) in row] for row in ev_probe])  # [steps][variant]
+        dom = int(np.argmax(probe_ms.mean(axis=0)))
+        if args.kernel_events == "dominant":
+            ev = [[p if i == dom else None for i, p in enumerate(row)] for row in ev]
+        for k in range(WARMUP_BLOCK):  # back under load after the host read the probe events
+            step(t_base + (warm + probe_steps + k) * 3600)
+        torch.cuda.synchronize()
+        warm += probe_steps + WARMUP_BLOCK
     warmup_s = time.perf_counter() - t_w
     if world > 1:
         dist.barrier()
@@ -552,7 +615,7 @@ def measure(wl, args, world, dist, comm, steps, warmup, t_base=0, cold=False):
     elapsed = time.perf_counter() - t0
     # per-variant mean kernel time: the timed steps where they carry events (the dominant
     # engine; every engine with --kernel-events all), the event-timed warm-up block otherwise
-    kern_mean = probe_ms.mean(axis=0)
+    kern_mean = probe_ms.mean(axis=0) if probe else None
     timed = {} if group else {i: np.array([row[i][0].elapsed_time(row[i][1]) for row in ev])
                               for i in range(nv) if ev and ev[0][i] is not None}
     # device time per grouped step: the launch plus the kernel boundary to the next (~0-1.5 us;
@@ -637,7 +700,9 @@ def main():
     # does not apply and the step runs them as fcx_run
     args.group = int(bool(args.group) and la is not None and len(variants) >= 2 and (args.types == 1 or not f32)
                      and (args.max_blocks is None or args.max_blocks <= 0))
-    m = measure(wl, args, world, dist, coll, args.steps, args.warmup, t_base, cold=True)
+    m = measure(wl, args, world, dist, coll, args.steps, args.warmup, t_base, cold=args.full, probe=args.full)
+    if args.dump_outputs:  # before anything else runs: what the last timed step left
+        dump_outputs(wl, args.dump_outputs, rank, world)
     t_max = m["t_max"]
     ms_per_step = t_max / args.steps * 1e3
     cells_per_step = n_global * len(variants)
@@ -652,7 +717,7 @@ def main():
     else:
         dom_bytes, dom_ms = int(alg_bytes[dom]), float(mean_ms[dom])
     achieved = dom_bytes / (dom_ms * 1e-3) / 1e9
-    per_variant = {
+    per_variant = None if mean_ms is None else {
         v: {"kernel_ms": round(float(mean_ms[i]), 4),
             "alg_bytes": int(alg_bytes[i]),
             "bytes_per_cell": round(alg_bytes[i] / n, 3),
@@ -675,8 +740,8 @@ def main():
         except Exception:
             traffic = None
 
-    mg = multi_gpu_check(wl, world, rank, dist) if la is not None else None
-    ar = allreduce_cost(comm, wl, world, dist)
+    mg = multi_gpu_check(wl, world, rank, dist) if args.full and la is not None else None
+    ar = allreduce_cost(comm, wl, world, dist) if args.full else None
 
     out = {
         "metric": METRIC,
@@ -687,10 +752,10 @@ def main():
         "warmup": args.warmup,
         "ms_per_step": round(ms_per_step, 4),
         "warmup_run": {"steps": m["warm"], "seconds": round(m["warmup_s"], 3),
-                       "rule": f"at least --warmup steps and at least {MIN_WARMUP_S} s of device work, then an "
-                               "event-timed block (every engine) and one more block without events"},
+                       "rule": f"at least --warmup steps and at least {MIN_WARMUP_S} s of device work"
+                               + (", then an event-timed block (every engine) and one more block without events"
+                                  if per_variant is not None else "")},
         "timed_ms": round(t_max * 1e3, 3),
-        "cold_step_ms": round(m["cold_ms"], 4),
         "higher_is_better": True,
         "scaling": "strong" if args.global_cells else "weak",
         "vs_baseline": None,
@@ -748,13 +813,17 @@ def main():
                        "(picked in an event-timed warm-up block of every engine)" if args.kernel_events == "dominant"
                        else "HIP event pairs around every engine's launch in every timed step"),
         },
-        "kernels": per_variant,
-        "kernels_rule": ("kernel_ms of each variant's own launch, from the event-timed warm-up block (one launch per "
-                         "engine); the timed steps run them as one group launch" if grouped else
-                         "kernel_ms from the timed steps' events for " + ", ".join(variants[i] for i in m["timed_events"])
-                         + ("; from the event-timed warm-up block for the others" if len(m["timed_events"]) < len(variants)
-                            else "")),
     }
+    if m["cold_ms"] is not None:
+        out["cold_step_ms"] = round(m["cold_ms"], 4)
+    if per_variant is not None:
+        out["kernels"] = per_variant
+        out["kernels_rule"] = (
+            "kernel_ms of each variant's own launch, from the event-timed warm-up block (one launch per "
+            "engine); the timed steps run them as one group launch" if grouped else
+            "kernel_ms from the timed steps' events for " + ", ".join(variants[i] for i in m["timed_events"])
+            + ("; from the event-timed warm-up block for the others" if len(m["timed_events"]) < len(variants)
+               else ""))
     if mg is not None:
         out["multi_gpu_check"] = mg
     if ar is not None:
@@ -764,7 +833,7 @@ def main():
     torch.cuda.synchronize()
 
     # the same workload on the other atmosphere map (periodic: no carried segment, no fix-up)
-    if args.other_map and args.atmos:
+    if args.full and args.other_map and args.atmos:
         other = "periodic" if args.atmos_map == "random" else "random"
         wo = Workload(n_global, rank, world, variants, types=args.types, bias=args.bias, precision=args.precision,
                       atmos=True, caller_device=args.caller_device, device=gpu, atmos_map=other,
@@ -790,7 +859,7 @@ def main():
 
     # config 5's fp32 kernels on the same workload (N = 1): Mcells/s and the roofline fraction
     # of the step's one launch, next to the fp64 line
-    if args.config5 and world == 1 and not f32 and args.atmos:
+    if args.full and args.config5 and world == 1 and not f32 and args.atmos:
         w5 = Workload(n_global, rank, world, variants, types=args.types, bias=args.bias, precision="f32",
                       atmos=True, caller_device=args.caller_device, device=gpu, atmos_map=args.atmos_map,
                       stream=torch.cuda.current_stream(dev), engine_options=engine_options)
@@ -817,7 +886,7 @@ def main():
         torch.cuda.synchronize()
 
     # config 4 at this N: the fixed 40M-cell grid over the same ranks (strong scaling)
-    if args.config4 and not args.global_cells:
+    if args.full and args.config4 and not args.global_cells:
         w4 = Workload(args.config4, rank, world, variants, types=1, precision=args.precision,
                       atmos=bool(args.atmos), device=gpu, stream=torch.cuda.current_stream(dev),
                       engine_options=engine_options, atmos_map=args.atmos_map)
@@ -857,9 +926,9 @@ def main():
         del w4, wl
         torch.cuda.synchronize()
 
-    if rank == 0 and world == 1 and args.e2e:
+    if args.full and rank == 0 and world == 1 and args.e2e:
         out["e2e"] = e2e_host(args, variants)
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu:
         # the reference path on this box's host cores at BASELINE's config sizes: config 1/2's
         # Baltic-size grid (32,768 cells) and this workload's size, on one core (one MPI rank
         # of the reference) and on the box's CPU share as APPLE-range ranks (cpu_legs.py)

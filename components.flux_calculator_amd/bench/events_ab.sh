@@ -8,7 +8,7 @@ O=gpurun_out/${1:-events_ab}
 mkdir -p $O
 for r in 1 2; do
   for m in all dominant; do
-    timeout -k 10 200 python3 bench.py --steps 200 --warmup 200 --no-cpu --e2e 0 --other-map 0 --config4 0 \
+    timeout -k 10 200 python3 bench.py --full --steps 200 --warmup 200 --no-cpu --e2e 0 --other-map 0 --config4 0 \
       --kernel-events $m > $O/bench_${m}_$r.json || exit $?
   done
 done

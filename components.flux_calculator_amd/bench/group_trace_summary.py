@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Mean duration of the timed group launches of each bench.py workload in a rocprofv3 kernel
-trace of `bench.py --no-cpu --e2e 0` (measurement tool).
+trace of `bench.py --full --no-cpu --e2e 0` (measurement tool).
 
 The bench's workloads run one after the other: main (random map, 10M cells), other_map
 (periodic), config5_fp32 (the fp32 engine, round 6), config4 (40M cells), each as build + cold + warm-up + event-timed per-engine

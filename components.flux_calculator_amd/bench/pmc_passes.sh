@@ -9,7 +9,7 @@ O=gpurun_out/${1:-pmc}
 mkdir -p $O
 for c in FETCH_SIZE WRITE_SIZE; do
   d=$( [ $c = FETCH_SIZE ] && echo fetch || echo write )
-  timeout -s KILL 120 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/t1/$d -o run -- python3 bench.py --steps 5 --warmup 1 --no-cpu --config4 0 > /dev/null
-  timeout -s KILL 120 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/t2/$d -o run -- python3 bench.py --steps 3 --warmup 1 --no-cpu --config4 0 --types 2 > /dev/null
+  timeout -s KILL 120 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/t1/$d -o run -- python3 bench.py --full --steps 5 --warmup 1 --no-cpu --config4 0 > /dev/null
+  timeout -s KILL 120 rocprofv3 --pmc $c --kernel-trace --output-format csv -d $O/t2/$d -o run -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu --config4 0 --types 2 > /dev/null
 done
 echo done > $O/DONE

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Per-phase kernel statistics of one `rocprofv3 --kernel-trace` run of bench.py.
 
-A default bench line times three workloads one after the other: the main one (`value`,
+A `bench.py --full` line times three workloads one after the other: the main one (`value`,
 `roofline`), the `other_map` sub-object and the `config4` sub-object.  rocprof's
 `kernel_stats.csv` averages every dispatch of a kernel name over all three, so it cannot be
 compared with the roofline's mean kernel time.  This tool splits the kernel trace of the same

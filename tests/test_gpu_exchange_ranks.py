@@ -295,7 +295,8 @@ def test_bench_two_ranks_through_libfcx_exchange(tmp_path):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--same-device", "--backend", "gloo", "--collective", "rccl", "--steps", "6",
-           "--warmup", "2", "--cells", "1000000", "--config4", "2000000", "--no-cpu", "--e2e", "0"]
+           "--warmup", "2", "--cells", "1000000", "--config4", "2000000", "--no-cpu", "--e2e", "0",
+           "--full"]  # multi_gpu_check and config 4 are --full's
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     line = json.loads([x for x in r.stdout.splitlines() if x.startswith("{")][-1])
