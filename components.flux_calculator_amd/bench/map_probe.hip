@@ -15,6 +15,16 @@
 //   5 as 3, the block's four waves' atmosphere values staged in LDS and stored by the block
 //     after a barrier, so only the lines at the block's two ends are shared with other
 //     workgroups
+//   6 as 3, but the atmosphere pool holds one record per atmosphere cell ([a][field], 48 B):
+//     the wave's six runs become one contiguous run of ~1.5 KB (2 partial lines, not 12);
+//     store form (a): every segment-start lane stores its record as three 16-B non-temporal
+//     stores
+//   7 as 6, store form (b): the wave parks its records in a wave-private LDS row by segment
+//     ordinal (popcount of the start ballot below the lane) and stores the run densely, 16 B
+//     per lane (valid when the wave's segments are consecutive atmosphere cells, which they
+//     always are here; no barrier, the row belongs to one wave)
+// After the timing, layouts 3, 6 and 7 run once more writing 8 * cell + field so that the host can
+// check that every atmosphere value landed where its layout says.
 // Every layout is measured on several fresh allocation sets (physical placement moves a
 // many-stream kernel by several per cent) in an interleaved order.  Measurement only.
 //   hipcc --offload-arch=gfx950 -O3 map_probe.hip -o map_probe && ./map_probe
@@ -56,7 +66,9 @@ __device__ __forceinline__ unsigned xcd_block(unsigned b, unsigned nb) {
   return i / K * row + x * K + i % K;
 }
 
-template <int L>
+constexpr int kMaxRun = 48;  // 32 + the two offsets in [-8, 8): at most 47 atmosphere cells per wave
+
+template <int L, bool V = false>
 __global__ __launch_bounds__(256) void step(Args a) {
   const long tile = (long)xcd_block(blockIdx.x, gridDim.x) * 4 + (threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
@@ -118,11 +130,45 @@ __global__ __launch_bounds__(256) void step(Args a) {
     (void)lo_hi;
     return;
   }
+  if (L == 6) {  // records, three 16-B stores per segment-start lane
+    if (lane < a1 - a0) {
+      const long av = a0 + lane;
+      d2 *rec = reinterpret_cast<d2 *>(a.atm + av * kA);
+#pragma unroll
+      for (int k = 0; k < kA; k += 2) {
+        const d2 v = V ? d2{(double)(av * 8 + k), (double)(av * 8 + k + 1)} : d2{q * (k + 2), q * (k + 3)};
+        __builtin_nontemporal_store(v, rec + k / 2);
+      }
+    }
+    return;
+  }
+  if (L == 7) {  // records, parked in the wave's LDS row by ordinal, stored densely
+    __shared__ d2 park[4][kMaxRun * kA / 2];
+    d2 *row_ = park[threadIdx.x >> 6];
+    const bool start = lane < a1 - a0;
+    const unsigned long long starts = __ballot(start);
+    const int ord = __popcll(starts & ((1ull << lane) - 1));
+    const int cnt = __popcll(starts);
+    if (start) {
+      const long av = a0 + lane;
+#pragma unroll
+      for (int k = 0; k < kA; k += 2)
+        row_[ord * (kA / 2) + k / 2] =
+            V ? d2{(double)(av * 8 + k), (double)(av * 8 + k + 1)} : d2{q * (k + 2), q * (k + 3)};
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    d2 *run = reinterpret_cast<d2 *>(a.atm + a0 * kA);
+    for (int c = lane; c < cnt * (kA / 2); c += 64) __builtin_nontemporal_store(row_[c], run + c);
+    return;
+  }
   if (lane < a1 - a0) {
     const long av = a0 + lane, u = av / kTile, ao = av % kTile;
 #pragma unroll
     for (int k = 0; k < kA; ++k) {
-      if (L == 4) a.atm[(u * kA + k) * kTile + ao] = q * (k + 2);
+      if (V) a.atm[(u * kA + k) * kTile + ao] = (double)(av * 8 + k);
+      else if (L == 4) a.atm[(u * kA + k) * kTile + ao] = q * (k + 2);
       else __builtin_nontemporal_store(q * (k + 2), a.atm + (u * kA + k) * kTile + ao);
     }
   }
@@ -133,13 +179,14 @@ int main() {
   const long natm = n / 4 + 64, atiles = (natm + kTile - 1) / kTile + 1;
   const double alg = (kR + kW) * 8.0 + 12.0 + kA * 8.0 / 4.0;  // B/cell
   const int sets = 4, reps = 30;
-  std::vector<double> best[6], mean[6];
+  std::vector<double> best[8], mean[8];
+  bool ok = true;
   hipEvent_t e0, e1;
   CHECK(hipEventCreate(&e0));
   CHECK(hipEventCreate(&e1));
   const int blocks = (int)((n / 128 + 3) / 4);
   for (int set = 0; set < sets; ++set) {
-    for (int L : {0, 3, 4, 5}) {
+    for (int L : {0, 3, 6, 7}) {
       const long S = L == 1 ? kR + 2 : kR;
       double *rd, *wr, *atm, *w = nullptr;
       int *idx = nullptr;
@@ -163,6 +210,8 @@ int main() {
         else if (L == 3) hipLaunchKernelGGL(step<3>, dim3(blocks), dim3(256), 0, 0, a);
         else if (L == 4) hipLaunchKernelGGL(step<4>, dim3(blocks), dim3(256), 0, 0, a);
         else if (L == 5) hipLaunchKernelGGL(step<5>, dim3(blocks), dim3(256), 0, 0, a);
+        else if (L == 6) hipLaunchKernelGGL(step<6>, dim3(blocks), dim3(256), 0, 0, a);
+        else if (L == 7) hipLaunchKernelGGL(step<7>, dim3(blocks), dim3(256), 0, 0, a);
         else hipLaunchKernelGGL(step<2>, dim3(blocks), dim3(256), 0, 0, a);
       };
       for (int i = 0; i < 200; ++i) launch();  // clocks up
@@ -183,6 +232,22 @@ int main() {
       mean[L].push_back(alg * n / (m * 1e-3) / 1e9);
       printf("set %d layout %d: mean %.1f GB/s, best %.1f GB/s\n", set, L, mean[L].back(), best[L].back());
       fflush(stdout);
+      if (set == 0 && (L == 3 || L >= 6)) {  // every value where its layout says?
+        if (L == 3) hipLaunchKernelGGL((step<3, true>), dim3(blocks), dim3(256), 0, 0, a);
+        else if (L == 6) hipLaunchKernelGGL((step<6, true>), dim3(blocks), dim3(256), 0, 0, a);
+        else hipLaunchKernelGGL((step<7, true>), dim3(blocks), dim3(256), 0, 0, a);
+        const long last = n / 128 * 32 - 8;  // (the last wave's run ends within 8 cells of n / 4)
+        std::vector<double> h(atiles * kA * kTile);
+        CHECK(hipMemcpy(h.data(), atm, h.size() * 8, hipMemcpyDeviceToHost));
+        long bad = 0;
+        for (long av = 0; av < last; ++av)
+          for (int k = 0; k < kA; ++k) {
+            const double got = L == 3 ? h[(av / kTile * kA + k) * kTile + av % kTile] : h[av * kA + k];
+            bad += got != (double)(av * 8 + k);
+          }
+        printf("layout %d: %ld of %ld atmosphere values misplaced\n", L, bad, last * kA);
+        ok = ok && bad == 0;
+      }
       CHECK(hipFree(rd));
       CHECK(hipFree(wr));
       CHECK(hipFree(atm));
@@ -190,12 +255,16 @@ int main() {
       if (L == 0 || L >= 3) CHECK(hipFree(w));
     }
   }
-  const char *names[6] = {"separate", "in read pool", "map pool", "atmosphere ranges misaligned",
-                          "misaligned, temporal atmosphere stores", "misaligned, block-staged atmosphere stores"};
-  for (int L : {0, 3, 4, 5}) {
+  const char *names[8] = {"separate", "in read pool", "map pool", "atmosphere ranges misaligned",
+                          "misaligned, temporal atmosphere stores", "misaligned, block-staged atmosphere stores",
+                          "misaligned, 48-B records, three 16-B stores per start lane",
+                          "misaligned, 48-B records, parked in LDS and stored densely"};
+  for (int L : {0, 3, 6, 7}) {
     double m = 0;
     for (double x : mean[L]) m += x;
-    printf("layout %d (%s): mean over %d sets %.1f GB/s\n", L, names[L], sets, m / sets);
+    const auto mm = std::minmax_element(mean[L].begin(), mean[L].end());
+    printf("layout %d (%s): mean over %d sets %.1f GB/s, sets %.1f..%.1f\n", L, names[L], sets, m / sets,
+           *mm.first, *mm.second);
   }
-  return 0;
+  return ok ? 0 : 2;
 }

@@ -251,6 +251,16 @@ struct fcx_engine {
   bool exchanged = false;           // ... and its boundary slots completed (comm attached)
   void *atm_pool = nullptr;
   int64_t atm_out_tpad = 0;  // tile-blocked atmosphere outputs (kernels: tiled(a, atm_out_tpad))
+  // Per-cell atmosphere records (FCX_OPT_ATM_RECORDS): atm_pool holds one record of every
+  // registered field per atmosphere cell, [a][field], which the kernels write (field k at
+  // atm_pool + k, cells atm_fields.size() elements apart); the downloads read the tile-blocked
+  // pool of plain arrays atm_soa (layout atm_out_tpad), allocated at the first download and
+  // filled from the records by atm_unpack before every one.
+  int atm_records_opt = 2;   // 0 never, 1 wherever the layout applies, 2 auto
+  bool atm_records = false;  // the layout is in use (decided at fcx_commit)
+  void *atm_soa = nullptr;
+  size_t atm_soa_bytes = 0;
+  int atm_soa_sp = -1;       // its staging pool (StagePool::dev set when atm_soa is allocated)
   bool atmos_in_run = true;
   bool atm_done_fused = false;  // the last fcx_run already accumulated the atmosphere fields
   int group_members = 0;        // engines in the merged launch of its last run (0: fcx_run)
@@ -415,6 +425,10 @@ extern "C" int fcx_create(int device, int num_surface_types, const int32_t grid_
   e->device = device;
   e->T = num_surface_types;
   for (int g = 0; g < 3; ++g) e->n[g] = grid_size[g];
+  // FCX_ATM_RECORDS=0|1|2: the default of FCX_OPT_ATM_RECORDS (an explicit option still wins),
+  // so that a whole test suite can run with the record layout wherever it applies
+  if (const char *v = std::getenv("FCX_ATM_RECORDS"))
+    if ((*v == '0' || *v == '1' || *v == '2') && !v[1]) e->atm_records_opt = *v - '0';
   *out = e;
   return FCX_OK;
 }
@@ -450,6 +464,7 @@ extern "C" int fcx_destroy(fcx_engine *e) {
   (void)hipFree(e->d_atm_col);
   (void)hipFree(e->d_atm_w);
   (void)hipFree(e->atm_pool);
+  (void)hipFree(e->atm_soa);
   (void)hipFree(e->atm_shared_own);
   for (auto &r : e->remaps) {
     (void)hipFree(r.d_row);
@@ -804,7 +819,11 @@ static void plan_fused_atmos(fcx_engine *e, Plan &pl, uint32_t stages, int phase
   af.left = e->atm_left;
   af.right = e->atm_right;
   af.tpad = e->tpad;
-  af.out_tpad = e->atm_out_tpad;
+  af.out_tpad = e->atm_records ? 0 : e->atm_out_tpad;
+  af.out_stride = e->atm_records ? (int32_t)e->atm_fields.size() : 1;
+  // the records hold exactly the six fluxes in slot order: a halo wave stores its run densely
+  af.rec_dense = e->atm_records && af.out_stride == kFusedFields && nf == kFusedFields;
+  for (int k = 0; k < kFusedFields && af.rec_dense; ++k) af.rec_dense = af.out[k] == af.out[0] + k;
   pl.af = af;
   pl.atm_nf = nf;
   pl.atm_phase = phase;
@@ -1791,9 +1810,12 @@ static void stage_setup(fcx_engine *e) {
     cand.push_back(StagePool{(char *)p, nullptr, e->tiled_bytes, true, (size_t)kLayoutTile * es,
                              (size_t)(kLayoutTile + e->tpad) * es});
   if (e->pool) cand.push_back(StagePool{(char *)e->pool, nullptr, e->pool_bytes, false, 0, 0});
+  int atm_cand = -1;  // records: the pool the downloads read does not exist yet (atm_unpack)
   if (e->atm_pool) {
     const bool t = e->atm_out_tpad != 0;
-    cand.push_back(StagePool{(char *)e->atm_pool, nullptr, e->atm_pool_bytes, t, t ? (size_t)kLayoutTile * es : 0,
+    if (e->atm_records) atm_cand = (int)cand.size();
+    cand.push_back(StagePool{e->atm_records ? nullptr : (char *)e->atm_pool, nullptr,
+                             e->atm_records ? e->atm_soa_bytes : e->atm_pool_bytes, t, t ? (size_t)kLayoutTile * es : 0,
                              t ? (size_t)(kLayoutTile + e->atm_out_tpad) * es : 0});
   }
   for (auto &rm : e->remaps)
@@ -1808,16 +1830,32 @@ static void stage_setup(fcx_engine *e) {
   for (auto &bf : e->bufs)
     if (!bf.external && heap(bf.host, bf.n)) mark(bf.dev);
   for (auto &f : e->atm_fields)
-    if (!f.external && heap(f.out_host, e->n_atmos)) mark(f.out_dev);
+    if (!f.external && heap(f.out_host, e->n_atmos)) {
+      if (atm_cand >= 0)
+        used[(size_t)atm_cand] = 1;
+      else
+        mark(f.out_dev);
+    }
   for (auto &rm : e->remaps)
     for (auto &f : rm.fields)
       if (!f.external && heap(f.out_host, rm.n_dst)) mark(f.out_dev);
   for (size_t i = 0; i < cand.size(); ++i)
-    if (used[i]) e->spools.push_back(cand[i]);
+    if (used[i]) {
+      if ((int)i == atm_cand) e->atm_soa_sp = (int)e->spools.size();
+      e->spools.push_back(cand[i]);
+    }
   for (auto &bf : e->bufs)
     if (!bf.external && heap(bf.host, bf.n)) bf.st = stage_ref(e, bf.dev);
-  for (auto &f : e->atm_fields)
-    if (!f.external && heap(f.out_host, e->n_atmos)) f.st = stage_ref(e, f.out_dev);
+  for (size_t k = 0; k < e->atm_fields.size(); ++k) {
+    auto &f = e->atm_fields[k];
+    if (f.external || !heap(f.out_host, e->n_atmos)) continue;
+    if (e->atm_soa_sp >= 0) {  // field k's slot of the tile-blocked shadow
+      f.st.sp = e->atm_soa_sp;
+      f.st.soff = k * (size_t)kLayoutTile * es;
+    } else {
+      f.st = stage_ref(e, f.out_dev);
+    }
+  }
   for (auto &rm : e->remaps)
     for (auto &f : rm.fields)
       if (!f.external && heap(f.out_host, rm.n_dst)) f.st = stage_ref(e, f.out_dev);
@@ -2312,12 +2350,35 @@ extern "C" int fcx_commit(fcx_engine *e) {
     const int64_t nfa = (int64_t)e->atm_fields.size();
     if (FCX_TILED_ATM && e->tpad && !atm_ext && nfa >= 2 && e->n_atmos > 0) {
       const int64_t tiles = (e->n_atmos + kLayoutTile - 1) / kLayoutTile;
-      e->atm_pool_bytes = (size_t)tiles * nfa * kLayoutTile * e->esize;
-      HIP_TRY(hipMalloc(&e->atm_pool, e->atm_pool_bytes));
-      for (int64_t k = 0; k < nfa; ++k)
-        e->atm_fields[k].out_dev = reinterpret_cast<double *>((char *)e->atm_pool + (size_t)k * kLayoutTile * e->esize);
+      const size_t soa_bytes = (size_t)tiles * nfa * kLayoutTile * e->esize;
       e->atm_out_tpad = (nfa - 1) * kLayoutTile;
       need = 0;
+      // Per-cell records instead (FCX_OPT_ATM_RECORDS): fp64, engine-owned outputs.  The
+      // tile-blocked pool is then the downloads' shadow, allocated at the first download
+      // (atm_unpack), and the kernels write the records.  Auto: where the whole-grid launch is
+      // the halo launch that stores a wave's records as one dense run (one surface type, the
+      // six fluxes, a map with crossings whose segments the halo covers: full_range_halo) --
+      // every other launch stores the records value by value at a 48-B stride, which measured
+      // far slower than the arrays (periodic map, no crossings: 1.097 against 0.712 ms per group
+      // launch, profiles/r07/full/) -- and from two pipeline chunks of exchange cells: below, a
+      // step is dispatch-bound and downloads every time, and the unpack launch before the
+      // download would cost it more than the kernel gains.
+      const int halo_h = (e->atm_maxseg - 1 + 1) / 2;
+      const bool dense_launch = e->T == 1 && nfa == kFusedFields && e->atm_contiguous && e->atm_halo &&
+                                e->atm_crossings > 0 && halo_h >= 1 && halo_h <= 4;
+      e->atm_records = !e->f32 && (e->atm_records_opt == 1 ||
+                                   (e->atm_records_opt == 2 && dense_launch && e->n[0] >= 2 * e->min_chunk));
+      if (e->atm_records) {
+        e->atm_soa_bytes = soa_bytes;
+        e->atm_pool_bytes = ((size_t)e->n_atmos * nfa * sizeof(double) + 255) / 256 * 256;
+        HIP_TRY(hipMalloc(&e->atm_pool, e->atm_pool_bytes));
+        for (int64_t k = 0; k < nfa; ++k) e->atm_fields[k].out_dev = reinterpret_cast<double *>(e->atm_pool) + k;
+      } else {
+        e->atm_pool_bytes = soa_bytes;
+        HIP_TRY(hipMalloc(&e->atm_pool, e->atm_pool_bytes));
+        for (int64_t k = 0; k < nfa; ++k)
+          e->atm_fields[k].out_dev = reinterpret_cast<double *>((char *)e->atm_pool + (size_t)k * kLayoutTile * e->esize);
+      }
     }
     if (need) {
       e->atm_pool_bytes = need;
@@ -2547,6 +2608,8 @@ static int launch_plan(fcx_engine *e, Plan *pl, const double *corr_m, int64_t lo
 static int regrid_var(fcx_engine *e, int var, int surface_type);
 static int comm_exchange(fcx_engine *e);
 static hipError_t get_atm(const fcx_engine *e, double *host, const double *dev, hipStream_t s);
+static int atm_unpack(fcx_engine *e, hipStream_t s);
+static const double *atm_src(const fcx_engine *e, size_t k);
 static int run_remaps(fcx_engine *e, int phase);
 static int download_remaps(fcx_engine *e, int phase, hipStream_t s, std::vector<Xfer> *xs);
 
@@ -2706,13 +2769,19 @@ extern "C" int fcx_download(fcx_engine *e, int phase) {
   stage_prepare_outputs(e);
   std::vector<Xfer> xs;  // every staged download of the phase in one set of DMAs
   std::vector<int> ids = pl->writes;
-  for (auto &f : e->atm_fields)
+  bool any_atm = false;
+  for (auto &f : e->atm_fields) any_atm = any_atm || (f.phase & phase);
+  if (any_atm)
+    if (int r = atm_unpack(e, e->stream)) return r;
+  for (size_t k = 0; k < e->atm_fields.size(); ++k) {
+    auto &f = e->atm_fields[k];
     if ((f.phase & phase) && e->n_atmos > 0) {
       if (f.st.sp >= 0)
         xs.push_back(xfer_of(f.st, f.out_host, e->n_atmos));
       else if (!f.external)
-        HIP_TRY(get_atm(e, f.out_host, f.out_dev, e->stream));
+        HIP_TRY(get_atm(e, f.out_host, atm_src(e, k), e->stream));
     }
+  }
   if (int r = download_remaps(e, phase, e->stream, &xs)) return r;
   if (e->any_regrid) {  // device-side regrid destinations of the fields this phase computes
     std::vector<int> extra;
@@ -2748,6 +2817,26 @@ static hipError_t get_atm(const fcx_engine *e, double *host, const double *dev, 
   return hipSuccess;
 }
 
+// Per-cell records (FCX_OPT_ATM_RECORDS): before a download on stream s, the records are
+// unpacked into the tile-blocked pool of plain arrays the downloads read (allocated here, at
+// the first download: an engine whose host never downloads holds the records only).
+static int atm_unpack(fcx_engine *e, hipStream_t s) {
+  if (!e->atm_records || e->n_atmos <= 0) return FCX_OK;
+  if (!e->atm_soa) {
+    HIP_TRY(hipMalloc(&e->atm_soa, e->atm_soa_bytes));
+    if (e->atm_soa_sp >= 0) e->spools[(size_t)e->atm_soa_sp].dev = reinterpret_cast<char *>(e->atm_soa);
+  }
+  const int r = launch_atm_unpack(reinterpret_cast<const double *>(e->atm_pool), reinterpret_cast<double *>(e->atm_soa),
+                                  e->n_atmos, (int)e->atm_fields.size(), e->atm_out_tpad, s);
+  if (r) return fail(FCX_E_HIP, "atm_unpack launch: %s", hipGetErrorString((hipError_t)r));
+  return FCX_OK;
+}
+// where the downloads read atmosphere field k (after atm_unpack)
+static const double *atm_src(const fcx_engine *e, size_t k) {
+  if (!e->atm_records) return e->atm_fields[k].out_dev;
+  return reinterpret_cast<const double *>(reinterpret_cast<const char *>(e->atm_soa) + k * (size_t)kLayoutTile * e->esize);
+}
+
 static AtmosArgs atmos_args(fcx_engine *e, int phase) {
   AtmosArgs a{};
   a.f32 = e->f32 ? 1 : 0;
@@ -2760,7 +2849,8 @@ static AtmosArgs atmos_args(fcx_engine *e, int phase) {
   a.right = e->atm_right;
   a.shared = e->atm_shared;
   a.tpad = e->tpad;
-  a.out_tpad = e->atm_out_tpad;
+  a.out_tpad = e->atm_records ? 0 : e->atm_out_tpad;
+  a.out_stride = e->atm_records ? (int64_t)e->atm_fields.size() : 1;
   a.vec = a.col == nullptr && e->aligned16;
   for (size_t i = 0; i < e->atm_fields.size(); ++i) {
     const auto &f = e->atm_fields[i];
@@ -2797,6 +2887,7 @@ static int run_remaps(fcx_engine *e, int phase) {
     a.n_atmos = rm.n_dst;
     a.left = a.right = -1;
     a.tpad = e->tpad;
+    a.out_stride = 1;  // a remap's outputs are plain arrays
     auto flush = [&]() -> int {
       if (!a.nf) return FCX_OK;
       a.rec = nullptr;
@@ -3140,14 +3231,21 @@ static int step_pipelined(fcx_engine *e, int phase, int32_t t, Plan *pl) {
   HIP_TRY(hipEventRecord(e->ev_comp[K - 1], e->stream));
   HIP_TRY(hipStreamWaitEvent(e->s_out, e->ev_comp[K - 1], 0));
   std::vector<Xfer> xa;  // atmosphere and remap outputs
-  if (e->atmos_in_run || e->atm_done_fused)
-    for (auto &f : e->atm_fields)
+  if (e->atmos_in_run || e->atm_done_fused) {
+    bool any_atm = false;
+    for (auto &f : e->atm_fields) any_atm = any_atm || (f.phase & phase);
+    if (any_atm)
+      if (int r = atm_unpack(e, e->s_out)) return r;
+    for (size_t k = 0; k < e->atm_fields.size(); ++k) {
+      auto &f = e->atm_fields[k];
       if ((f.phase & phase) && e->n_atmos > 0) {
         if (f.st.sp >= 0)
           xa.push_back(xfer_of(f.st, f.out_host, e->n_atmos));
         else if (!f.external)
-          HIP_TRY(get_atm(e, f.out_host, f.out_dev, e->s_out));
+          HIP_TRY(get_atm(e, f.out_host, atm_src(e, k), e->s_out));
       }
+    }
+  }
   if (int r = download_remaps(e, phase, e->s_out, &xa)) return r;
   if (!xa.empty()) {
     if (int r = stage_alloc(e, xa)) return r;
@@ -3514,6 +3612,11 @@ extern "C" int fcx_set_option(fcx_engine *e, int option, int64_t value) {
       if (value < 0 || value > 2) return fail(FCX_E_ARG, "remap_pack: 0 never, 1 always, 2 auto");
       e->remap_pack = (int)value;
       return FCX_OK;
+    case FCX_OPT_ATM_RECORDS:
+      if (e->committed) return fail(FCX_E_STATE, "atm_records is applied at fcx_commit");
+      if (value < 0 || value > 2) return fail(FCX_E_ARG, "atm_records: 0 never, 1 always, 2 auto");
+      e->atm_records_opt = (int)value;
+      return FCX_OK;
     case FCX_OPT_TILED_LAYOUT:
       if (e->committed) return fail(FCX_E_STATE, "tiled_layout is applied at fcx_commit");
       e->tiled_opt = value != 0;
@@ -3650,6 +3753,13 @@ extern "C" int fcx_run_atmos(fcx_engine *e, int phase) {
     e->atm_done = true;
   }
   return comm_exchange(e);  // no-op without a communicator, or when fcx_run already exchanged
+}
+
+extern "C" int fcx_atm_records(const fcx_engine *e, int32_t *on) {
+  if (!e || !on) return fail(FCX_E_ARG, "NULL argument");
+  if (!e->committed) return fail(FCX_E_STATE, "the atmosphere output layout is decided at fcx_commit");
+  *on = e->atm_records ? 1 : 0;
+  return FCX_OK;
 }
 
 extern "C" int fcx_last_group_size(fcx_engine *e, int32_t *members) {

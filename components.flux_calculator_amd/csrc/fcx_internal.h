@@ -114,6 +114,11 @@ struct AvgRegs {
 constexpr int kLayoutShift = FCX_LAYOUT_SHIFT;
 constexpr int64_t kLayoutTile = int64_t(1) << kLayoutShift;
 __host__ __device__ inline int64_t tiled(int64_t j, int64_t tpad) { return j + (j >> kLayoutShift) * tpad; }
+// Element of atmosphere cell a in an atmosphere output array.  Two layouts: the arrays of
+// their own or the tile-blocked pool (stride 1, tpad), and per-cell records
+// (FCX_OPT_ATM_RECORDS: field k's array starts at pool + k, the cells are `stride` = fields
+// per record elements apart, tpad 0).
+__host__ __device__ inline int64_t atm_at(int64_t a, int64_t stride, int64_t tpad) { return tiled(a, tpad) * stride; }
 
 struct Params {
   int64_t n[3];          // cells per grid
@@ -177,6 +182,7 @@ struct AtmosArgs {
                            // products and sums stay fp64 (OASIS maps in double)
   int64_t tpad;            // layout of the x fields (engine buffers)
   int64_t out_tpad;        // layout of out: the engine's tiled atmosphere pool, or 0
+  int64_t out_stride = 1;  // ... elements between atmosphere cells (atm_at): 1, or the record length
   int32_t vec;             // col == nullptr and every x 16-B aligned: vector staging loads
   int32_t rec_p;           // elements per record of rec (nf rounded up to a 16-B multiple)
   const void *rec;         // remap gather: the x fields packed cell-major (pack_records),
@@ -239,6 +245,10 @@ struct AtmosFused {
   int32_t stride, left, right;
   int64_t tpad;        // layout of x (engine buffers); idx, w are contiguous
   int64_t out_tpad;    // layout of out (tiled atmosphere pool, or 0)
+  int32_t out_stride = 1;  // ... elements between atmosphere cells (atm_at): 1, or the record length
+  int32_t rec_dense;   // out is one record of exactly the kFusedFields fluxes per cell, in slot
+                       // order (out[k] == out[0] + k, out_stride == kFusedFields, 16-B aligned):
+                       // the halo launch stores a wave's run of records densely
   int32_t scol[kFusedFields];  // shared-slot column of fused field k (AtmosArgs::scol)
   int64_t n_tiles;     // tiles [lo / tile cells, n_tiles) of one launch (set per launch, so no
                        // wave divides by the halo-dependent tile size)
@@ -293,6 +303,9 @@ int launch_cells_group(GroupMember *members, int n, const LaunchConfig &lc, void
 // the segments carried over a tile boundary: carry of tile t-1 + the head cells of tile t,
 // for every tile of a launch of n_cells (fp32: 256-cell tiles of float fields)
 int launch_atmos_fixup(const AtmosFused &af, int64_t n_cells, bool f32, void *stream);
+// atmosphere records -> the tile-blocked pool the downloads read: soa[f][tiled(a, tpad)] =
+// rec[a * nf + f], a < n_atmos (fp64; rec and soa 16-B aligned)
+int launch_atm_unpack(const double *rec, double *soa, int64_t n_atmos, int nf, int64_t tpad, void *stream);
 // zero the fused outputs of the n atmosphere cells in cells[] (cells without exchange cells)
 int launch_atmos_zero(const AtmosFused &af, const int32_t *cells, int64_t n, bool f32, void *stream);
 // the fix-ups of several engines' fused launches (fcx_run_group members) as one launch

@@ -817,13 +817,55 @@ __device__ __forceinline__ void segment_done(const AtmosFused &af, int64_t tile,
 #pragma unroll
   for (int k = 0; k < kFusedFields; ++k) {
     if (!af.out[k]) continue;
-    FCX_GLOBAL R *o = gptr(reinterpret_cast<R *>(af.out[k]) + tiled(a, af.out_tpad));
+    FCX_GLOBAL R *o = gptr(reinterpret_cast<R *>(af.out[k]) + atm_at(a, af.out_stride, af.out_tpad));
     if constexpr (sizeof(R) == 8)
       __builtin_nontemporal_store((R)acc[k], o);
     else
       *o = (R)acc[k];
     if (a == 0 && af.left >= 0) gptr(af.shared)[(int64_t)af.left * af.stride + af.scol[k]] = acc[k];
     if (a == af.n_atmos - 1 && af.right >= 0) gptr(af.shared)[(int64_t)af.right * af.stride + af.scol[k]] = acc[k];
+  }
+}
+
+// One round of segment sums of a halo wave tile into per-cell records (AtmosFused::rec_dense):
+// lane `act` holds the six sums of the segment of atmosphere cell a.  Measured on the fused
+// step's access shape (bench/map_probe.hip, profiles/r07/map_probe_records.txt): the run
+// parked in the wave's LDS rows by segment ordinal and stored densely, 16 B per lane, 6.35
+// TB/s against 6.20 for the six per-field runs; every start lane storing its own record as
+// three 16-B stores, 5.61.  So: dense when the round's segments are consecutive atmosphere
+// cells (a map without empty atmosphere cells inside the wave) and the product rows are free
+// (`last`: no further round reads them); the per-lane records otherwise.
+__device__ __forceinline__ void record_round(const AtmosFused &af, int32_t a, const double *acc, bool act, bool last,
+                                             double *wp) {
+  if (FCX_DBG_ATM_NOSTORE) return;
+  const int lane = threadIdx.x & 63;
+  const uint64_t am = __ballot(act);
+  const int ord = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(am >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)am, 0u));
+  const int cnt = __popcll(am);
+  const int32_t a_first = __builtin_amdgcn_readlane(a, __builtin_amdgcn_readfirstlane(first_bit(am) & 63));
+  const bool dense = last && __ballot(act && a != a_first + ord) == 0;
+  if (dense) {
+    wave_sync();  // every lane has read its products: the rows are free
+    if (act) {
+#pragma unroll
+      for (int q = 0; q < kFusedFields / 2; ++q)
+        reinterpret_cast<d2 *>(wp)[ord * (kFusedFields / 2) + q] = d2{acc[2 * q], acc[2 * q + 1]};
+    }
+    wave_sync();
+    FCX_GLOBAL d2 *run = gptr(reinterpret_cast<d2 *>(af.out[0] + (int64_t)a_first * kFusedFields));
+    for (int c = lane; c < cnt * (kFusedFields / 2); c += 64)
+      __builtin_nontemporal_store(reinterpret_cast<const d2 *>(wp)[c], run + c);
+  } else if (act) {
+    FCX_GLOBAL d2 *rec = gptr(reinterpret_cast<d2 *>(af.out[0] + (int64_t)a * kFusedFields));
+#pragma unroll
+    for (int q = 0; q < kFusedFields / 2; ++q) __builtin_nontemporal_store(d2{acc[2 * q], acc[2 * q + 1]}, rec + q);
+  }
+  if (act) {
+#pragma unroll
+    for (int k = 0; k < kFusedFields; ++k) {
+      if (a == 0 && af.left >= 0) gptr(af.shared)[(int64_t)af.left * af.stride + af.scol[k]] = acc[k];
+      if (a == af.n_atmos - 1 && af.right >= 0) gptr(af.shared)[(int64_t)af.right * af.stride + af.scol[k]] = acc[k];
+    }
   }
 }
 
@@ -863,7 +905,8 @@ constexpr int atmos_waves() { return C == 4 ? FCX_F32_ATMOS_WAVES : FCX_ATMOS_WA
 // One wave tile of the fused kernel: the fluxes of the tile's cells (process), their
 // products w * x parked in the wave's LDS rows, the segment sums in rounds, the crossing
 // record.  wp: the wave's LDS region.
-template <int C, class R, int VAR, bool NT, int TM, bool RAVG, bool REC, bool HALO>
+// (HALO: 0 no, 1 halo tiles, 2 halo tiles storing per-cell records densely -- record_round)
+template <int C, class R, int VAR, bool NT, int TM, bool RAVG, bool REC, int HALO>
 __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const double *__restrict__ corr_m,
                                            const AtmosFused &af, int64_t tile, double *wp) {
   constexpr int kT = tile_cells<C>();  // cells per wave tile (lane l: cells C*l .. C*l+C-1)
@@ -933,7 +976,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
       next_cont = tend < n && gptr(af.idx)[tend] == gptr(af.idx)[tend - 1];
     }
     if (j0 < n)
-      process<C, true, VAR, NT, R, TM, RAVG, LdsEmitT<C>, REC, HALO>(
+      process<C, true, VAR, NT, R, TM, RAVG, LdsEmitT<C>, REC, (HALO != 0)>(
           P, corr_m, j0, emit, AccLds<C, R>{reinterpret_cast<R *>(wp + emit.s), kR}, t0 + kO);
     if constexpr (kXF) {  // the weights row of the fp32 fluxes (dead cells: weight 0)
 #pragma unroll
@@ -1038,8 +1081,30 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
       }
       rem = 0;
     }
+    // Per-cell records (AtmosFused::rec_dense, halo tiles): the round's sums are one record per
+    // segment, and the segments of a wave are as a rule consecutive atmosphere cells, so the
+    // wave's stores are ONE contiguous run of records (two partial 128-B lines, not two per
+    // field).  record_round stores it.
+    constexpr bool kDense = HALO == 2;
+    static_assert(!kDense || (sizeof(R) == 8 && C == 2 && !REC && !RAVG), "dense records: the fp64 T = 1 halo launch");
     while (__ballot(rem != 0)) {
-      if (rem) {
+      if constexpr (kDense) {
+        // every lane takes part in record_round, so the sum is written without a branch: a
+        // lane without a start sums nothing that is stored (its first product is read and
+        // dropped); the first cell's 0.0 + product is the loop's first step
+        const bool act = rem != 0;
+        const int i = act ? __builtin_ctz(rem) : 0;
+        rem &= rem - 1;
+        const int32_t ai = i ? a[C - 1] : a[0];
+        const int c = C * lane + i;
+        const int end = act ? seg_end(i) : c;
+        double acc[kFusedFields];
+        const double *q0 = wp + lds_slot(c);
+#pragma unroll
+        for (int k = 0; k < kFusedFields; ++k) acc[k] = 0.0 + q0[k * kR];
+        for (int e = c + 1; e < end; ++e) add_cell(acc, e);
+        record_round(af, ai, acc, act, __ballot(rem != 0) == 0, wp);
+      } else if (rem) {
         const int i = __builtin_ctz(rem);
         rem &= rem - 1;
         int32_t ai = a[0];
@@ -1090,7 +1155,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
     wave_sync();  // every lane is done reading before the next tile overwrites the region
 }
 
-template <int C, class R, int VAR, bool NT, int TM, bool RAVG, bool REC = false, bool HALO = false>
+template <int C, class R, int VAR, bool NT, int TM, bool RAVG, bool REC = false, int HALO = 0>
 // (REC: the record stores took CCLM to 129 VGPRs and 3 waves per SIMD; capped at 4 blocks = 4 waves)
 __global__ __launch_bounds__(64 * atmos_waves<C>(), RAVG  ? FCX_RAVG_ATMOS_BLOCKS
                                                   : REC ? 4
@@ -1153,7 +1218,7 @@ __global__ __launch_bounds__(64 * atmos_waves<C>(), RAVG  ? FCX_RAVG_ATMOS_BLOCK
 #ifndef FCX_GROUP_BLOCKS
 #define FCX_GROUP_BLOCKS 4
 #endif
-template <int C, class R, bool NT, bool HALO, int TM = 1, bool RAVG = false>
+template <int C, class R, bool NT, int HALO, int TM = 1, bool RAVG = false>
 __global__ __launch_bounds__(64 * atmos_waves<C>(), RAVG ? FCX_RAVG_ATMOS_BLOCKS
                                                     : C == 4 ? FCX_F32_ATMOS_BLOCKS : FCX_GROUP_BLOCKS) void
 cells_atmos_group_kernel(const GroupArgs g, const Params *__restrict__ P0, const Params *__restrict__ P1,
@@ -1189,6 +1254,10 @@ cells_atmos_group_kernel(const GroupArgs g, const Params *__restrict__ P0, const
       case 2: atmos_tile<C, R, 2, NT, TM, RAVG, false, HALO>(P, m.corr_m, m.af, tile, wp); break;
       default: atmos_tile<C, R, 3, NT, TM, RAVG, false, HALO>(P, m.corr_m, m.af, tile, wp); break;
     }
+    // launch_cells_group launches a wave per tile.  Said to the compiler for the dense-record
+    // variant: as a loop, it kept loop-invariant constants in registers across the body and
+    // spilled six of them at the 128-VGPR cap
+    if constexpr (HALO == 2) break;
   }
 }
 
@@ -1220,7 +1289,7 @@ __device__ __forceinline__ void fixup_one(const AtmosFused &af, int64_t t, int k
     if (e < h) acc = acc + p[e];
   const R *xk = reinterpret_cast<const R *>(af.x[k]);
   for (int e = kRecHead; e < h; ++e) acc = acc + af.w[x0 + e] * (double)xk[tiled(x0 + e, af.tpad)];
-  reinterpret_cast<R *>(af.out[k])[tiled(a, af.out_tpad)] = (R)acc;
+  reinterpret_cast<R *>(af.out[k])[atm_at(a, af.out_stride, af.out_tpad)] = (R)acc;
   if (a == 0 && af.left >= 0) af.shared[(int64_t)af.left * af.stride + af.scol[k]] = acc;
   if (a == af.n_atmos - 1 && af.right >= 0) af.shared[(int64_t)af.right * af.stride + af.scol[k]] = acc;
 }
@@ -1373,7 +1442,7 @@ __global__ __launch_bounds__(256) void atmos_kernel(const AtmosArgs a) {
 #pragma unroll
   for (int f = 0; f < kMaxAtmosFields; ++f) {
     if (f >= a.nf) break;
-    reinterpret_cast<R *>(a.out[f])[tiled(c, a.out_tpad)] = (R)acc[f];
+    reinterpret_cast<R *>(a.out[f])[atm_at(c, a.out_stride, a.out_tpad)] = (R)acc[f];
     if (c == 0 && a.left >= 0) a.shared[(int64_t)a.left * a.stride + a.scol[f]] = acc[f];
     if (c == a.n_atmos - 1 && a.right >= 0) a.shared[(int64_t)a.right * a.stride + a.scol[f]] = acc[f];
   }
@@ -1433,7 +1502,7 @@ __global__ void atmos_finish_kernel(const AtmosArgs a, int32_t n_boundaries) {
   if (t < a.nf) {
     R *out = reinterpret_cast<R *>(a.out[t]);
     if (a.left >= 0) out[0] = (R)a.shared[(int64_t)a.left * a.stride + a.scol[t]];
-    if (a.right >= 0) out[tiled(a.n_atmos - 1, a.out_tpad)] = (R)a.shared[(int64_t)a.right * a.stride + a.scol[t]];
+    if (a.right >= 0) out[atm_at(a.n_atmos - 1, a.out_stride, a.out_tpad)] = (R)a.shared[(int64_t)a.right * a.stride + a.scol[t]];
   }
   __syncthreads();
   for (int64_t i = t; i < (int64_t)n_boundaries * a.stride; i += blockDim.x) a.shared[i] = 0.0;
@@ -1449,7 +1518,7 @@ __global__ void atmos_finish_group_kernel(const FinishGroup g) {
   if (t < a.nf) {
     R *out = reinterpret_cast<R *>(a.out[t]);
     if (a.left >= 0) out[0] = (R)a.shared[(int64_t)a.left * a.stride + a.scol[t]];
-    if (a.right >= 0) out[tiled(a.n_atmos - 1, a.out_tpad)] = (R)a.shared[(int64_t)a.right * a.stride + a.scol[t]];
+    if (a.right >= 0) out[atm_at(a.n_atmos - 1, a.out_stride, a.out_tpad)] = (R)a.shared[(int64_t)a.right * a.stride + a.scol[t]];
   }
   __syncthreads();
   for (int64_t i = t; i < (int64_t)n_boundaries * a.stride; i += blockDim.x) a.shared[i] = 0.0;
@@ -1522,7 +1591,7 @@ static void launch_r(const Params *hp, const LaunchConfig &lc, int blocks, hipSt
     launch_c<C, R, 0, false>(lc, blocks, s, dp, corr_m, lo, hi);
 }
 
-template <int C, class R, int VAR, int TM, bool RAVG, bool REC = false, bool HALO = false>
+template <int C, class R, int VAR, int TM, bool RAVG, bool REC = false, int HALO = 0>
 static void launch_atm(bool nt, int blocks, hipStream_t s, const Params *dp, const double *corr_m,
                        const AtmosFused &af, int64_t lo, int64_t hi) {
   if (nt)
@@ -1553,7 +1622,9 @@ static int launch_atm_r(const Params *hp, const LaunchConfig &lc, int blocks, hi
     else
       launch_atm<2, double, VAR, 1, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
   } else if (hp->num_types == 1) {
-    if (halo)
+    if (halo && af.rec_dense)
+      launch_atm<2, double, VAR, 1, false, false, 2>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+    else if (halo)
       launch_atm<2, double, VAR, 1, false, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
     else
       launch_atm<2, double, VAR, 1, false>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
@@ -1665,6 +1736,15 @@ static void launch_group_h(bool halo, bool ravg, int blocks, hipStream_t s, cons
     if (ravg) {  // several surface types, the type-0 averages in registers (no halo tiles)
       hipLaunchKernelGGL((cells_atmos_group_kernel<C, R, NT, false, 0, true>), dim3(blocks),
                          dim3(64 * atmos_waves<C>()), 0, s, g, p[0], p[1], p[2], p[3]);
+      return;
+    }
+  }
+  if constexpr (C == 2 && sizeof(R) == 8) {
+    bool dense = halo;  // every member keeps per-cell records of the six fluxes
+    for (int k = 0; k < g.n; ++k) dense = dense && g.m[k].af.rec_dense;
+    if (dense) {
+      hipLaunchKernelGGL((cells_atmos_group_kernel<C, R, NT, 2>), dim3(blocks), dim3(64 * atmos_waves<C>()), 0, s, g,
+                         p[0], p[1], p[2], p[3]);
       return;
     }
   }
@@ -1793,6 +1873,42 @@ int launch_atmos_fixup(const AtmosFused &af, int64_t n, bool f32, void *stream) 
 
 // Atmosphere cells without exchange cells: the sequential SCRIP sum over no links is 0, and
 // the fused launch, which stores one value per segment, has none for them.
+// Atmosphere records -> the tile-blocked pool of plain arrays that the downloads read
+// (FCX_OPT_ATM_RECORDS): a block takes 256 atmosphere cells (one layout tile holds them all),
+// loads their contiguous records with 16-B loads into LDS and writes each field's 256 values.
+__global__ __launch_bounds__(256) void atm_unpack_kernel(const double *__restrict__ rec, double *__restrict__ soa,
+                                                         int64_t n_atmos, int nf, int64_t tpad) {
+  constexpr int CB = 256;
+  extern __shared__ unsigned char lds_raw[];
+  double *lds = reinterpret_cast<double *>(lds_raw);  // [CB][nf]
+  const int64_t c0 = (int64_t)blockIdx.x * CB;
+  const int cn = (int)min((int64_t)CB, n_atmos - c0);
+  const int ne = cn * nf;
+  const double *src = rec + c0 * nf;  // 16-B aligned: c0 is even
+  for (int e = 2 * (int)threadIdx.x; e < ne; e += 2 * CB) {
+    if (e + 1 < ne) {
+      const d2 v = __builtin_nontemporal_load(reinterpret_cast<const d2 *>(src + e));
+      lds[e] = v[0];
+      lds[e + 1] = v[1];
+    } else {
+      lds[e] = src[e];
+    }
+  }
+  __syncthreads();
+  const int t = threadIdx.x;
+  if (t >= cn) return;
+  double *dst = soa + tiled(c0, tpad) + t;
+  for (int f = 0; f < nf; ++f) dst[(int64_t)f * kLayoutTile] = lds[t * nf + f];
+}
+
+int launch_atm_unpack(const double *rec, double *soa, int64_t n_atmos, int nf, int64_t tpad, void *stream) {
+  if (n_atmos <= 0 || nf <= 0) return 0;
+  const unsigned blocks = (unsigned)((n_atmos + 255) / 256);
+  hipLaunchKernelGGL(atm_unpack_kernel, dim3(blocks), dim3(256), (size_t)256 * nf * sizeof(double),
+                     reinterpret_cast<hipStream_t>(stream), rec, soa, n_atmos, nf, tpad);
+  return (int)hipGetLastError();
+}
+
 template <class R>
 __global__ __launch_bounds__(256) void atmos_zero_kernel(const AtmosFused af, const int32_t *cells, int64_t n) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1800,7 +1916,7 @@ __global__ __launch_bounds__(256) void atmos_zero_kernel(const AtmosFused af, co
   const int32_t a = cells[i];
 #pragma unroll
   for (int k = 0; k < kFusedFields; ++k)
-    if (af.out[k]) reinterpret_cast<R *>(af.out[k])[tiled(a, af.out_tpad)] = R(0);
+    if (af.out[k]) reinterpret_cast<R *>(af.out[k])[atm_at(a, af.out_stride, af.out_tpad)] = R(0);
 }
 
 int launch_atmos_zero(const AtmosFused &af, const int32_t *cells, int64_t n, bool f32, void *stream) {

@@ -94,6 +94,7 @@ SIGNATURES = [
     ("fcx_device_free", _I, [_P]),
     ("fcx_memcpy", _I, [_P, _P, _c.c_size_t, _I]),
     ("fcx_last_group_size", _I, [_P, _c.POINTER(_I32)]),
+    ("fcx_atm_records", _I, [_P, _c.POINTER(_I32)]),
     ("fcx_step_async", _I, [_P, _I, _I32]),
     ("fcx_upload_field", _I, [_P, _I, _I, _I]),
     ("fcx_comm_verify", _I, [_P, _I]),

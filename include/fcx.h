@@ -159,6 +159,9 @@ int fcx_run_group(fcx_engine *const *engines, int n_engines, int phase, int32_t 
  * attached communicator, remaps) runs in LIST order whichever engines were merged, so the
  * per-engine collectives of fcx_set_comm keep the same order on every rank. */
 int fcx_last_group_size(fcx_engine *e, int32_t *members);
+/* after fcx_commit: 1 when the engine keeps its atmosphere outputs as per-cell records
+ * (FCX_OPT_ATM_RECORDS), 0 when as plain arrays */
+int fcx_atm_records(const fcx_engine *e, int32_t *on);
 /* the three above; with host-bound fields pipelined over cell chunks (FCX_OPT_PIPELINE_CHUNKS) */
 int fcx_step(fcx_engine *e, int phase, int32_t current_step_time);
 /* waits for the engine's stream; the caller's host arrays hold the downloaded outputs once it
@@ -384,6 +387,22 @@ enum fcx_option {
                                    scattered values.  2 auto (default): launches of >= 2
                                    fields; 1: always; 0: never (gather from the arrays).
                                    Applied at fcx_commit (scratch of cells x record)      */
+  FCX_OPT_ATM_RECORDS = 21,     /* engine-owned atmosphere outputs on the device as one record
+                                   per atmosphere cell ([cell][field]) instead of one array
+                                   per field: a wave of the fused flux launch then stores its
+                                   segment sums as one contiguous run.  The host arrays are
+                                   plain arrays as ever: fcx_download unpacks the records on
+                                   the device first (one more launch per download).  2 auto
+                                   (default): exchange grids of >= 2 x PIPELINE_MIN_CHUNK
+                                   cells whose whole-grid launch is the halo launch of one
+                                   surface type and the six fluxes (FCX_OPT_ATMOS_HALO; any
+                                   other launch stores the records value by value, slower
+                                   than arrays); 1: wherever the layout applies; 0: never.  It
+                                   applies to fp64 engines with tile-blocked mirrors and >= 2
+                                   atmosphere fields, none of them the caller's device
+                                   memory or used in place.  Applied at fcx_commit; the
+                                   environment variable FCX_ATM_RECORDS (0, 1, 2) sets the
+                                   default                                                  */
   FCX_OPT_TILED_LAYOUT = 11     /* engine-owned mirrors tile-blocked (default 1): tiles of
                                    4096 cells, the read-only arrays' tiles interleaved in
                                    one pool and the written arrays' in another, so a wave's
