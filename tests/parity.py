@@ -2,6 +2,8 @@
     max_j |x - x_ref| / max(|x_ref[j]|, 1e-6 * ||x_ref||_inf)  <=  1e-10
 (mixed abs/rel, normalised per field: pure elementwise relative error is ill-posed where
 q_s - q_a or T_s - T_a*EF cancel).  Integer/index results are compared bit-exactly.
+Beside it, assert_tight (below) holds every fp64 output cell to a bit-exact, a seeded bit-exact
+or a derived few-eps gate.
 """
 import numpy as np
 
@@ -196,6 +198,274 @@ def conditioned_full(case, got, ref, t, label, tol=FP64_TOL, ulps=16, trials=8):
         if np.any(err > allow):
             problems.append(f"{k}: {int(np.sum(err > allow))} of {cells.size} cells over the gate are not explained "
                             f"by input rounding (first {cells[err > allow][:4].tolist()})")
+    if problems:
+        raise AssertionError(f"{label}: " + "; ".join(problems))
+    return out
+
+
+# --------------------------------------------------------------------------------------
+# Tight fp64 gates: bit-exact, seeded-exact and derived-bound (beside the 1e-10 gate above)
+# --------------------------------------------------------------------------------------
+EPS = 2.0 ** -52
+EXACT, SEEDED, BOUND, BUILT = "exact", "seeded-exact", "derived-bound", "construction"
+QSUR_CAP = 8.0  # |d| <= 8 eps |ref|
+HSEN_CAP = (4.0, 4.0)  # |d| <= 4 eps |F c_p T_a EF| + 4 eps |ref|
+MEVA_RCO_CAP = (6.0, 4.0)  # |d| <= 6 eps |rho_a c_aw vel q_w| + 4 eps |ref|
+
+_FLUX_TABLE = {"MEVA": "which_flux_mass_evap", "HLAT": "which_flux_heat_latent",
+               "HSEN": "which_flux_heat_sensible", "UMOM": "which_flux_momentum",
+               "VMOM": "which_flux_momentum", "RBBR": "which_flux_radiation_blackbody"}
+_QSUR_TABLE = {1: "which_spec_vapor_surface_t", 2: "which_spec_vapor_surface_u",
+               3: "which_spec_vapor_surface_v"}
+# flux_constants.F90:13-32 and the RCO formulas' own constants (scale terms of the bounds only)
+_CP, _LV, _LS, _RD, _RV, _UMIN = 1005.0, 2.501e6, 2.835e6, 287.05, 461.51, 0.01
+
+
+def bits_equal(a, b):
+    """Per cell: equal bit patterns through an int64 view (-0.0 != +0.0); NaN matches NaN
+    whatever the payload, and never a number."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    if a.shape != b.shape:
+        raise AssertionError(f"shape {a.shape} != {b.shape}")
+    na, nb = np.isnan(a), np.isnan(b)
+    return (na & nb) | (~na & ~nb & (a.view(np.int64) == b.view(np.int64)))
+
+
+def _method(case, s, g, name):
+    """The method that computes (s, g, name); a 'copy' alias takes the method of the aliased
+    type-1 field (prepare:36-38)."""
+    table = _QSUR_TABLE[g] if name == "QSUR" else _FLUX_TABLE[name]
+    m = case.methods[table][s - 1].rstrip()
+    if m == "copy":
+        m = case.methods[table][0].rstrip()
+        if m == "copy":
+            raise AssertionError(f"({s},{g},{name}): 'copy' of a 'copy'")
+    return m
+
+
+def _bias_additions(case, s):
+    """How often calc:112-116 adds the bias to the MEVA array of type s: once per surface type
+    whose MEVA slot is that array and whose method is not 'none'."""
+    if case.corrections is None:
+        return 0
+    a = case.lf.field[(s, 1, "MEVA")]
+    return sum(1 for i in range(1, case.num_surface_types + 1)
+               if case.lf.field.get((i, 1, "MEVA")) is a
+               and case.methods["which_flux_mass_evap"][i - 1].rstrip() != "none")
+
+
+def gate_of(case, key):
+    """The gate that holds the output field key = (s, g, name), from the case's method tables.
+    Raises for a field that none of the gates covers."""
+    s, g, name = key
+    T = case.num_surface_types
+    if s == 0:  # a type-0 average: as exact as the weakest of the per-type fields it sums
+        if name == "TSUR":
+            return EXACT
+        parts = {gate_of(case, (i, g, name)) for i in range(1, T + 1)}
+        if parts <= {EXACT}:
+            return EXACT
+        return SEEDED if parts <= {EXACT, SEEDED} else BUILT
+    if name == "RSDR":
+        return EXACT
+    if name not in _FLUX_TABLE and name != "QSUR":
+        raise AssertionError(f"{key}: no gate for this field")
+    m = _method(case, s, g, name)
+    if m == "zero":
+        return EXACT
+    if name == "RBBR" and m == "StBo":
+        return EXACT
+    if name == "QSUR" and m == "CCLM":
+        return BOUND
+    if name == "MEVA" and m in ("CCLM", "MOM5"):
+        return SEEDED
+    if name == "MEVA" and m == "RCO":
+        if _bias_additions(case, s) > 1:
+            raise AssertionError(f"{key}: RCO MEVA with the bias added more than once (a 'copy' alias) "
+                                 "has no derived bound")
+        return BOUND
+    if name == "HLAT" and m in ("water", "ice"):
+        return {EXACT: EXACT, SEEDED: SEEDED, BOUND: BUILT}[gate_of(case, (s, 1, "MEVA"))]
+    if name == "HSEN" and m in ("CCLM", "MOM5"):
+        return BOUND
+    if name in ("HSEN", "UMOM", "VMOM") and m == "RCO":
+        return EXACT
+    if name in ("UMOM", "VMOM") and m in ("CCLM", "MOM5"):
+        return SEEDED
+    raise AssertionError(f"{key}: method {m!r} is in none of the gates")
+
+
+def seeded_case(case, got):
+    """The case with every which_spec_vapor_surface_{t,u,v} method 'none' and the QSUR arrays
+    replaced by the device's own QSUR outputs (aliases kept: with shared grids the u and v
+    slots are the t array, with separate grids each grid is seeded from its own array)."""
+    import copy
+
+    from fcx.local_field import LocalFields
+
+    seeds = {id(case.lf.field[k]): np.array(got[k], dtype=np.float64, copy=True)
+             for k in got if k[2] == "QSUR"}
+    lf = LocalFields(case.lf.grid_size)
+    lf.field = {k: (seeds.get(id(a), a) if k[2] == "QSUR" else a) for k, a in case.lf.field.items()}
+    lf.allocated = set(case.lf.allocated)
+    lf.put_to = dict(case.lf.put_to)
+    new = copy.copy(case)
+    new.lf = lf
+    new.methods = {k: (["none"] * len(v) if k.startswith("which_spec_vapor_surface") else list(v))
+                   for k, v in case.methods.items()}
+    return new
+
+
+def _host(a):
+    return a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()
+
+
+def _bound_cap(case, key, ref):
+    """The per-cell cap of a derived-bound field, its scale term in numpy from the inputs."""
+    s, g, name = key
+    f = lambda v: np.asarray(_host(case.lf.field[(s, g, v)]), dtype=np.float64)  # noqa: E731
+    ref = np.abs(np.asarray(ref, dtype=np.float64))
+    if name == "QSUR":
+        return QSUR_CAP * EPS * ref
+    vel = np.sqrt(f("UATM") * f("UATM") + f("VATM") * f("VATM"))
+    if name == "HSEN":
+        a = f("AMOI" if _method(case, s, g, name) == "CCLM" else "CHEA")
+        ps, ts = f("PSUR"), f("TSUR")
+        rate = a * np.maximum(vel, _UMIN) * ps / (_RD * ts * (1.0 + (_RV / _RD - 1.0) * f("QATM")))
+        ef = (ps / f("PATM")) ** (_RD / _CP)
+        return HSEN_CAP[0] * EPS * np.abs(rate * _CP * f("TATM") * ef) + HSEN_CAP[1] * EPS * ref
+    if name == "MEVA":
+        ts = f("TSUR")
+        q_w = 0.62197 * (6.1078E+02 * np.exp(17.269 * (ts - 273.15) / (ts - 35.86))) / 1.013E+05
+        return MEVA_RCO_CAP[0] * EPS * np.abs(1.225 * 1.15E-03 * vel * q_w) + MEVA_RCO_CAP[1] * EPS * ref
+    raise AssertionError(f"{key}: no derived bound")
+
+
+def assert_tight(case, got, ref, t, label, report=True):
+    """Every cell of every output of a fp64 case in one of three gates, each far inside the
+    1e-10 gate, none using the perturbation allowance.  got = the device's outputs, ref = the
+    plain oracle's (oracle_lib.run_case(case, "c", current_step_time=t)); case = the host case
+    (for device-resident runs its host twin).  eps = 2**-52; "bit-identical" = equal int64
+    views (-0.0 != +0.0), NaN cells equal NaN cells.
+
+    The device and the oracle run the same IEEE operations in the same order except at three
+    sites of fcx_physics.h: the exp of qsur_cclm, the exp of meva_rco and pow_exner =
+    exp(y log x) against the oracle's pow.  Fields (by the case's method tables; a 'copy' alias
+    is the aliased type-1 array and takes its class):
+
+    exact         bit-identical to ref.  RBBR, RSDR, the TSUR average, HSEN/UMOM/VMOM of the RCO
+                  method, every 'zero' method, the averages of these.
+    seeded-exact  bit-identical to a second oracle run on seeded_case(): QSUR methods 'none',
+                  QSUR = the device's own output.  MEVA/UMOM/VMOM of CCLM and MOM5, HLAT over
+                  such a MEVA, their averages.  The bias (added once per aliased 'copy') is
+                  reproduced by that run.
+                  By construction, from the device's own values, for EVERY such field whatever
+                  its class: HLAT == MEVA_dev * L (kLv 'water', kLs 'ice'), and every type-0
+                  average == acc = 0; for s in type order: acc = acc + x_s * FARE_s in float64.
+                  This is the only per-cell gate of HLAT over an RCO MEVA and of the averages
+                  that sum a bounded field ("construction" in the report); it pins them exactly
+                  given their bounded inputs.
+    derived-bound per cell against ref, scale terms in numpy from the inputs:
+                  QSUR (CCLM)       |d| <= 8 eps |ref|
+                  HSEN (CCLM, MOM5) |d| <= 4 eps |F c_p T_a EF| + 4 eps |ref|
+                  MEVA (RCO)        |d| <= 6 eps |rho_a c_aw vel q_w| + 4 eps |ref|
+
+    Derivation of the caps.  ROCm documents 1 ulp for fp64 exp and log, glibc's exp and pow are
+    within 1 ulp, and one ulp of x is at most eps |x|; so two results of exp on the same
+    argument differ by at most 2 eps relative.  A rounded operation on both sides (each result
+    within eps/2) adds at most eps to a relative difference; constants and inputs are the same
+    bits on both sides.
+      QSUR: e = p0 * exp(.) 3 eps; c e 4 eps; ps - c' e: c' e (4 eps) is at most 0.02 of the
+        result (e < 5 kPa, ps > 90 kPa), 0.1 eps, plus its rounding 1.1 eps; the quotient
+        4 + 1.1 + 1 = 6.1 eps.  Cap 8.
+      HSEN: y log x with x = ps/pa in (1, 1.02): the 1.5-ulp error of the argument is below
+        1e-2 eps absolute, so exp(y log x) is within 1.01 ulp of x**y and the oracle's pow
+        within 1; EF lies in [1, 2), where an ulp is eps: 2.0 eps.  T_a EF 3.0 eps.  The
+        difference T_s - T_a EF moves by 3.0 eps |T_a EF| and is rounded (eps of itself); the
+        product with F c_p (same bits) adds eps: |d| <= 3.0 eps |F c_p T_a EF| + 2 eps |ref|
+        (3.0 + 3 if F c_p is allowed a rounding of its own).  Caps 4 + 4.  F = a max(vel, u_min) p_s / (R_d T_s (1 + (R_v/R_d - 1) q_a)): the
+        reference passes q_a for the surface humidity here (flux_calculator_calculate P3).
+      MEVA (RCO): e_w = r exp(.) 3 eps; q_w = eps_c e_w / p_0 two operations, 5 eps;
+        q_w - q_a moves by 5 eps |q_w| and is rounded; the product with rho_a c_aw vel and at
+        most ONE bias addition round again: |d| <= 5 eps |K q_w| + 3 eps |ref| with K = rho_a
+        c_aw vel.  Caps 6 + 4.  (The two roundings before the bias are relative to the value
+        before it; they stay inside the caps while 2 |bias| <= |K q_w| + |ref|.  With the bias
+        added twice, a 'copy' alias, there is no such bound: gate_of() refuses that case.)
+    The caps are not fitted to any device output and are not to be raised for one.
+
+    Returns {"s:g:NAME": {"gate", "cells", "bit_identical_share", "worst_ratio", "failed_cells"}}
+    (bit_identical_share: against the seeded run for a seeded-exact field, else against ref;
+    worst_ratio: |d| / cap of a bounded field; failed_cells: {gate: cells}, empty when green),
+    writes it with write_report as ulp_gate_<label>.json (also when it fails), and raises an
+    AssertionError that lists every failing field with its gate and cell count."""
+    import oracle_lib
+
+    assert set(got) == set(ref), f"{label}: outputs {sorted(set(got) ^ set(ref))} on one side only"
+    gates = {k: gate_of(case, k) for k in ref}  # raises for an unclassified field
+    assert set(gates) == set(case.outputs), f"{label}: fields of the case in no gate"
+    dev = {id(case.lf.field[k]): np.asarray(got[k], dtype=np.float64) for k in got}
+    value = lambda k: dev.get(id(case.lf.field[k]), _host(case.lf.field[k]))  # noqa: E731
+    seeded = None
+    if SEEDED in gates.values():
+        seeded = oracle_lib.run_case(seeded_case(case, got), "c", current_step_time=t)
+    out, problems = {}, []
+
+    def fail(rec, key, gate, ok, what):
+        idx = np.nonzero(~ok)[0]
+        rec["failed_cells"][gate] = rec["failed_cells"].get(gate, 0) + int(idx.size)
+        g = np.asarray(got[key])
+        problems.append(f"{key} [{gate}] {what}: {idx.size} of {ok.size} cells, first {idx[:6].tolist()}, "
+                        f"got {g[idx[:3]].tolist()}")
+
+    for key, gate in gates.items():
+        s, g, name = key
+        x, r = np.asarray(got[key], dtype=np.float64), np.asarray(ref[key], dtype=np.float64)
+        same = bits_equal(x, r)
+        rec = {"gate": gate, "cells": int(x.size), "bit_identical_share": float(same.mean()) if x.size else 1.0,
+               "worst_ratio": 0.0, "failed_cells": {}}
+        covered = np.zeros(x.shape, dtype=bool)
+        if gate == EXACT:
+            covered[:] = True
+            if not same.all():
+                fail(rec, key, gate, same, "differs from the oracle")
+        elif gate == SEEDED:
+            covered[:] = True
+            ok = bits_equal(x, seeded[key])
+            rec["bit_identical_share"] = float(ok.mean()) if x.size else 1.0
+            if not ok.all():
+                fail(rec, key, gate, ok, "differs from the oracle seeded with the device's QSUR")
+        elif gate == BOUND:
+            covered[:] = True
+            cap = _bound_cap(case, key, r)
+            d = np.abs(x - r)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                ratio = np.where(d == 0.0, 0.0, d / cap)
+            ratio = np.where(np.isnan(x) & np.isnan(r), 0.0, ratio)
+            ratio = np.where(np.isnan(ratio), np.inf, ratio)  # NaN on one side only
+            ok = ratio <= 1.0
+            rec["worst_ratio"] = float(ratio.max(initial=0.0))
+            if not ok.all():
+                fail(rec, key, gate, ok, f"over its cap (worst ratio {rec['worst_ratio']:.3g})")
+        # by construction, from the device's own values
+        if s >= 1 and name == "HLAT" and _method(case, s, g, name) in ("water", "ice"):
+            covered[:] = True
+            L = _LV if _method(case, s, g, name) == "water" else _LS
+            ok = bits_equal(x, value((s, 1, "MEVA")) * L)
+            if not ok.all():
+                fail(rec, key, BUILT, ok, f"is not MEVA_dev * {L}")
+        if s == 0:
+            covered[:] = True
+            acc = np.zeros(x.shape)
+            for i in range(1, case.num_surface_types + 1):
+                acc = acc + value((i, g, name)) * _host(case.lf.field[(i, g, "FARE")])
+            ok = bits_equal(x, acc)
+            if not ok.all():
+                fail(rec, key, BUILT, ok, "is not the in-order sum of x_s * FARE_s of the device's x_s")
+        assert covered.all(), f"{label}: {key} has cells in no gate"
+        out["%d:%d:%s" % key] = rec
+    if report:
+        write_report("ulp_gate_" + "".join(c if c.isalnum() or c in "-_." else "_" for c in label), out)
     if problems:
         raise AssertionError(f"{label}: " + "; ".join(problems))
     return out

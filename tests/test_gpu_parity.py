@@ -9,7 +9,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
-from parity import assert_parity, cell_report, conditioned_full, write_report
+from parity import assert_parity, assert_tight, cell_report, conditioned_full, write_report
 
 pytestmark = pytest.mark.gpu
 
@@ -46,7 +46,9 @@ def fused(case, t=STEP_T, phases=(PHASE_ALL,)):
 def test_fused_t1(variant, bias, n):
     case = build_case(variant, n=n, T=1, bias=bias)
     ref = oracle_lib.run_case(case, "c", current_step_time=STEP_T)
-    assert_parity(fused(case), ref, label=case.name)
+    got = fused(case)
+    assert_parity(got, ref, label=case.name)
+    assert_tight(case, got, ref, STEP_T, f"{case.name}_n{n}")
 
 
 @pytest.mark.parametrize("variant", ["CCLM", "MOM5", "RCO"])
@@ -74,20 +76,26 @@ def test_fused_t1_host_modes(variant, zero_copy):
 def test_fused_t3_averages(variant):
     case = build_case(variant, n=3001, T=3, bias=True)
     ref = oracle_lib.run_case(case, "c", current_step_time=STEP_T)
-    assert_parity(fused(case), ref, label=case.name)
+    got = fused(case)
+    assert_parity(got, ref, label=case.name)
+    assert_tight(case, got, ref, STEP_T, f"{case.name}_n3001")
 
 
 def test_fused_ten_surface_types():
     case = build_case("MOM5", n=777, T=10, bias=True)
     ref = oracle_lib.run_case(case, "c", current_step_time=STEP_T)
-    assert_parity(fused(case), ref, label=case.name)
+    got = fused(case)
+    assert_parity(got, ref, label=case.name)
+    assert_tight(case, got, ref, STEP_T, f"{case.name}_n777")
 
 
 @pytest.mark.parametrize("variant", ["CCLM", "MOM5", "RCO"])
 def test_separate_uv_grids(variant):
     case = build_case(variant, n=2049, T=2, bias=False, sep_grids=(2101, 1999))
     ref = oracle_lib.run_case(case, "c", current_step_time=STEP_T)
-    assert_parity(fused(case), ref, label=case.name)
+    got = fused(case)
+    assert_parity(got, ref, label=case.name)
+    assert_tight(case, got, ref, STEP_T, f"{case.name}_n2049")
 
 
 @pytest.mark.parametrize("T", [1, 3])
