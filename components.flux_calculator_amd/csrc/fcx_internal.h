@@ -1,5 +1,6 @@
 // fcx_internal.h -- engine <-> kernel contract (device parameter block) of libfcx.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 #include "../../include/fcx.h"
 
@@ -35,6 +36,18 @@
 // halo tiles also for the multi-type kernel with register averages (A/B)
 #ifndef FCX_HALO_RAVG
 #define FCX_HALO_RAVG 0
+#endif
+// one s_waitcnt vmcnt(0) after a type's input loads in the single-type (TM = 1) kernels, in
+// straight-line code before the first flux block, so that no flux block waits for the stores
+// of the blocks before it (fcx_kernels.hip, process; 0 = A/B: the compiler's own waits)
+#ifndef FCX_INPUT_WAIT
+#define FCX_INPUT_WAIT 1
+#endif
+// the compacted map's dependent load of the segments' atmosphere cells issued right behind
+// that wait, in flight during the flux arithmetic (fcx_kernels.hip, atmos_tile; needs
+// FCX_INPUT_WAIT): 0 = after the flux pass
+#ifndef FCX_EARLY_SEG_ATM
+#define FCX_EARLY_SEG_ATM 0
 #endif
 // the fp64 launches' exchange -> atmosphere map (fp32 launches always read the compacted
 // one): 0 = a 4-B index per cell; 1 = the compacted map in halo launches, the index in
@@ -85,6 +98,20 @@ struct TypeParams {
   int8_t bias_adds;  // how many times corr(month) is added to MEVA (1 + #'copy' aliases)
   int8_t pad[7];
 };
+// The kernels read a type's method bytes as ONE aligned 64-bit word (m_qsur[0] in the low
+// byte ... m_rbbr in the high one) and bias_adds with its padding as the next 64-bit word
+// (fcx_kernels.hip, type_methods): wave-uniform scalar loads, where a byte member is a
+// vector load and a round trip (gfx950 has no byte-sized scalar load).  The layout they rely on:
+static_assert(offsetof(TypeParams, m_qsur) % 8 == 0 && offsetof(TypeParams, m_meva) == offsetof(TypeParams, m_qsur) + 3 &&
+                  offsetof(TypeParams, m_hlat) == offsetof(TypeParams, m_qsur) + 4 &&
+                  offsetof(TypeParams, m_hsen) == offsetof(TypeParams, m_qsur) + 5 &&
+                  offsetof(TypeParams, m_mom) == offsetof(TypeParams, m_qsur) + 6 &&
+                  offsetof(TypeParams, m_rbbr) == offsetof(TypeParams, m_qsur) + 7,
+              "TypeParams: the eight method bytes are one aligned 64-bit word");
+static_assert(offsetof(TypeParams, bias_adds) == offsetof(TypeParams, m_qsur) + 8 &&
+                  sizeof(TypeParams) == offsetof(TypeParams, bias_adds) + 8,
+              "TypeParams: bias_adds and its padding are the next aligned 64-bit word");
+static_assert(sizeof(TypeParams) % 8 == 0 && alignof(TypeParams) == 8, "TypeParams: 8-B aligned in Params::type[]");
 // type-0 average: X0 = sum_{s=1..T} X_s * FARE_s, in order (calc:376-383)
 struct AvgEntry {
   double *x0;
@@ -142,6 +169,11 @@ struct Params {
   int8_t rec_pos[6];
   int8_t pad3[2];
 };
+static_assert(offsetof(Params, type) % 8 == 0, "Params::type: the method words are 8-B aligned");
+// rec_pos and its padding are read as two aligned 32-bit words too (RecEmit)
+static_assert(offsetof(Params, rec_pos) % 4 == 0 && sizeof(Params) >= offsetof(Params, rec_pos) + 8 &&
+                  sizeof(Params::rec_pos) == 6,
+              "Params: rec_pos[6] + pad3[2] are two aligned 32-bit words");
 
 // launchers (fcx_kernels.hip); return hipError_t as int
 // how one cells_kernel launch is instantiated

@@ -111,6 +111,20 @@ __device__ __forceinline__ Vec<C, R> splat(R a) {
   return r;
 }
 
+// The value of a 'zero' method, formed where it is used.  As a plain constant the compiler
+// builds the 16-B register tuple of a zero store once, outside the tile loop, and keeps it
+// live through the whole flux pass for a branch that hardly ever runs: at the 128-VGPR cap of
+// the fp32 MOM5 fused kernel it was the one value spilled to scratch.  The empty asm makes
+// the zero opaque, so it is materialised inside the method's branch.  OPAQUE = false: the
+// plain constant (the multi-type kernels: there the opaque zero cost the C = 1 register-average
+// kernels 9-11 VGPRs and a wave per SIMD).
+template <int C, class R, bool OPAQUE>
+__device__ __forceinline__ Vec<C, R> zeros() {
+  R z = R(0);
+  if constexpr (OPAQUE) asm volatile("" : "+v"(z));
+  return splat<C, R>(z);
+}
+
 // The parameter block holds every field pointer as double*; in the fp32 engine the same
 // pointers address float arrays, so every access reinterprets them as R*.
 #define FOR_C _Pragma("unroll") for (int i = 0; i < C; ++i)
@@ -121,6 +135,45 @@ __device__ __forceinline__ Vec<C, R> splat(R a) {
 #define LD(p, j, n) ld<C, NT, R>(reinterpret_cast<const R *>(p) + D_, j, n)
 #define ST(p, j, n, ...) st<C, NT, R>(reinterpret_cast<R *>(p) + D_, j, n, __VA_ARGS__)
 
+// The wave-uniform method bytes of one surface type.  gfx950 has no byte-sized scalar load:
+// read as int8_t members, each byte is a vector load, a wait for it (and for every load and
+// store of the wave in flight) and a v_readfirstlane in the middle of the flux pass.  Read as
+// the two aligned 64-bit words the layout guarantees (fcx_internal.h), they are scalar loads
+// and the bytes are shifts.
+struct Methods {
+  int8_t qsur[3], meva, hlat, hsen, mom, rbbr;
+  int8_t bias_adds;
+};
+// The parameter block is not written while a launch runs, so its words may be read in the
+// constant address space: a uniform load there is a scalar load whatever the compiler can
+// prove about the stores around it.  (Read as global memory, the same words came back as
+// global_load_dwordx4 with a wait and v_readfirstlane: the char-typed copy may alias every
+// store of the kernel, and only a load known not to be clobbered is made scalar.)
+#define FCX_CONSTANT __attribute__((address_space(4)))
+typedef uint64_t __attribute__((aligned(8), may_alias)) word8_t;
+typedef uint32_t __attribute__((aligned(4), may_alias)) word4_t;
+template <class T>
+__device__ __forceinline__ const FCX_CONSTANT word8_t *cptr(const T *p) {
+  return (const FCX_CONSTANT word8_t *)p;
+}
+__device__ __forceinline__ int8_t byte_of(uint64_t w, int k) { return (int8_t)(uint8_t)(w >> (8 * k)); }
+__device__ __forceinline__ Methods type_methods(const TypeParams &tp) {
+  const uint64_t w = *cptr(&tp.m_qsur[0]), b = *cptr(&tp.bias_adds);
+  return Methods{{byte_of(w, 0), byte_of(w, 1), byte_of(w, 2)}, byte_of(w, 3), byte_of(w, 4),
+                 byte_of(w, 5),  byte_of(w, 6), byte_of(w, 7),  byte_of(b, 0)};
+}
+// The wait of the single-type kernels for a type's inputs: vmcnt(0) alone (expcnt and lgkmcnt
+// left at their maxima), as a builtin so that the compiler's wait-count pass sees it.
+__device__ __forceinline__ void wait_inputs() {
+#if FCX_INPUT_WAIT
+  __builtin_amdgcn_s_waitcnt(0x0F70);
+#endif
+}
+
+// process()'s `early` hook when the caller has nothing to issue behind the inputs' wait
+struct NoEarly {
+  __device__ __forceinline__ void operator()() const {}
+};
 // Momentum of one (type, u- or v-grid) cell group; `north` selects VMOM.
 struct NoEmit {
   template <int C, class R>
@@ -169,13 +222,14 @@ __device__ __forceinline__ void momentum(int8_t m, bool north, const UVGridPtrs 
 }
 
 // QSUR + momentum on one separate u or v grid (non-merged layout).
-template <int C, bool NT, class R>
-__device__ __forceinline__ void uv_grid(const TypeParams &tp, int k, uint32_t stages, int64_t j0,
+// TM = 1: one wait for the grid's inputs before its first store (process, wait_inputs).
+template <int C, bool NT, class R, int TM>
+__device__ __forceinline__ void uv_grid(const TypeParams &tp, const Methods &mt, int k, uint32_t stages, int64_t j0,
                                         int64_t n, int64_t D_) {
   const UVGridPtrs &g = tp.uv[k];
   const uint32_t s_qsur = k == 0 ? S_QSUR_U : S_QSUR_V;
   const uint32_t s_mom = k == 0 ? S_UMOM : S_VMOM;
-  const bool do_q = (stages & s_qsur) && tp.m_qsur[1 + k] == FCX_CCLM && g.qsur;
+  const bool do_q = (stages & s_qsur) && mt.qsur[1 + k] == FCX_CCLM && g.qsur;
   const bool do_m = (stages & s_mom) && g.mom;
   if (!do_q && !do_m) return;
   Vec<C, R> ts = {}, fi = {}, ps = {}, u = {}, v = {}, a = {}, qs = {};
@@ -188,10 +242,11 @@ __device__ __forceinline__ void uv_grid(const TypeParams &tp, int k, uint32_t st
   if (do_m) {  // ('zero' momentum binds no wind: the planner leaves uatm / vatm unset)
     if (g.uatm) u = LD(g.uatm, j0, n);
     if (g.vatm) v = LD(g.vatm, j0, n);
-    if (tp.m_mom == FCX_CCLM && g.amom) a = LD(g.amom, j0, n);
-    if (tp.m_mom == FCX_MOM5 && g.cmom) a = LD(g.cmom, j0, n);
+    if (mt.mom == FCX_CCLM && g.amom) a = LD(g.amom, j0, n);
+    if (mt.mom == FCX_MOM5 && g.cmom) a = LD(g.cmom, j0, n);
     if (g.qsur_in && !do_q) qs = LD(g.qsur_in, j0, n);
   }
+  if constexpr (TM == 1) wait_inputs();
   if (do_q) {
     FOR_C qs.v[i] = qsur_cclm(fi.v[i], ps.v[i], ts.v[i]);
     ST(g.qsur, j0, n, qs);
@@ -199,7 +254,7 @@ __device__ __forceinline__ void uv_grid(const TypeParams &tp, int k, uint32_t st
   if (do_m) {
     Vec<C, R> vel;
     FOR_C vel.v[i] = wind(u.v[i], v.v[i]);
-    momentum<C, NT, R>(tp.m_mom, k == 1, g, ts, ps, u, v, vel, qs, a, j0, n, D_);
+    momentum<C, NT, R>(mt.mom, k == 1, g, ts, ps, u, v, vel, qs, a, j0, n, D_);
   }
 }
 
@@ -261,12 +316,13 @@ struct RecEmit {
   const Inner &inner;
   R *rec;             // record of the lane's first cell
   int P;              // elements per record
-  const int8_t *pos;  // Params::rec_pos (wave-uniform)
+  uint64_t posw;      // Params::rec_pos (wave-uniform) as one word, position k in byte k
   int nv;             // cells of the lane inside the grid
 #ifndef FCX_REC_VEC  // 1: the values stay in registers and each record goes out as 16-B stores
 #define FCX_REC_VEC 1
 #endif
   mutable R vals[6][C];
+  __device__ __forceinline__ int pos(int k) const { return byte_of(posw, k); }
   template <int CC, class RR>
   __device__ __forceinline__ void operator()(int k, const Vec<CC, RR> &x) const {
     inner(k, x);
@@ -277,7 +333,7 @@ struct RecEmit {
       }
       return;
     }
-    const int p = pos[k];
+    const int p = pos(k);
     if (p >= 0) {
 #pragma unroll
       for (int i = 0; i < CC; ++i)
@@ -300,7 +356,7 @@ struct RecEmit {
           R v = R(0);
 #pragma unroll
           for (int k = 0; k < 6; ++k)
-            if (pos[k] == q * V + h) v = vals[k][i];
+            if (pos(k) == q * V + h) v = vals[k][i];
           t[h] = v;
         }
         *gptr(reinterpret_cast<VecT *>(rec + i * P + q * V)) = t;
@@ -320,11 +376,14 @@ struct RecEmit {
 // vanish); 0 = T from the parameter block.  RAVG (register averages) needs TM = 0.
 // HALO: cells at or past st_end are a halo tile's head cells -- their fluxes are computed for
 // the fused accumulation's products, nothing of them is stored (the next tile's wave stores).
+// early: called once the t-grid inputs of a single-type kernel have landed (TM = 1, after
+// wait_inputs): loads of the caller that depend on values requested with the inputs.
 template <int C, bool MERGED, int VAR, bool NT, class R = double, int TM = 1, bool RAVG = false,
-          class Emit = NoEmit, bool REC = false, bool HALO = false>
+          class Emit = NoEmit, bool REC = false, bool HALO = false, class Early = NoEarly>
 __device__ __forceinline__ void process(const Params *__restrict__ P, const double *__restrict__ corr_m,
                                         int64_t j0, const Emit &emit_in = Emit(),
-                                        AccLds<C, R> acc_lds = AccLds<C, R>{nullptr, 0}, int64_t st_end = 0) {
+                                        AccLds<C, R> acc_lds = AccLds<C, R>{nullptr, 0}, int64_t st_end = 0,
+                                        const Early &early = Early()) {
   static_assert(!(RAVG && TM), "register averages need more than one surface type");
   static_assert(!REC || (TM == 1 && !RAVG), "remap records: the T=1 launch");
   static_assert(!HALO || (TM == 1 && !RAVG) || (FCX_HALO_RAVG && RAVG), "halo tiles: the T=1 launch");
@@ -335,11 +394,15 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
   const bool do_t = j0 < nt;
   using SinkEmit = typename std::conditional<REC, RecEmit<C, R, Emit>, const Emit &>::type;
   SinkEmit emit = [&]() -> SinkEmit {
-    if constexpr (REC)
-      return RecEmit<C, R, Emit>{emit_in, reinterpret_cast<R *>(P->rec) + j0 * P->rec_p, P->rec_p, P->rec_pos,
+    if constexpr (REC) {
+      // (4-B aligned: two scalar words, like type_methods)
+      const FCX_CONSTANT word4_t *pw = (const FCX_CONSTANT word4_t *)&P->rec_pos[0];
+      const uint64_t posw = (uint64_t)pw[0] | ((uint64_t)pw[1] << 32);
+      return RecEmit<C, R, Emit>{emit_in, reinterpret_cast<R *>(P->rec) + j0 * P->rec_p, P->rec_p, posw,
                                  (int)max((int64_t)0, min((int64_t)C, ns - j0))};
-    else
+    } else {
       return emit_in;
+    }
   }();
   const int64_t D_ = (j0 >> kLayoutShift) * P->tpad;  // field layout shift of this lane's cells
   Vec<C, R> corr = {};  // the month slice is a plain contiguous array
@@ -422,13 +485,14 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
     }
     const TypeParams &tp = P->type[s];
     const TGridPtrs &g = tp.t;
+    const Methods mt = type_methods(tp);
     constexpr int8_t kVarMethod = VAR == 1 ? FCX_CCLM : VAR == 2 ? FCX_MOM5 : FCX_RCO;
-    const int8_t m_q = VAR ? (VAR == 3 ? FCX_NONE : FCX_CCLM) : tp.m_qsur[0];
-    const int8_t m_qu = VAR ? m_q : tp.m_qsur[1];
-    const int8_t m_qv = VAR ? m_q : tp.m_qsur[2];
-    const int8_t m_me = VAR ? kVarMethod : tp.m_meva;
-    const int8_t m_hs = VAR ? kVarMethod : tp.m_hsen;
-    const int8_t m_mo = VAR ? kVarMethod : tp.m_mom;
+    const int8_t m_q = VAR ? (VAR == 3 ? FCX_NONE : FCX_CCLM) : mt.qsur[0];
+    const int8_t m_qu = VAR ? m_q : mt.qsur[1];
+    const int8_t m_qv = VAR ? m_q : mt.qsur[2];
+    const int8_t m_me = VAR ? kVarMethod : mt.meva;
+    const int8_t m_hs = VAR ? kVarMethod : mt.hsen;
+    const int8_t m_mo = VAR ? kVarMethod : mt.mom;
     if (do_t) {
       // ---- every t-grid input this type needs (before any store of this type)
       Vec<C, R> qs = {}, me = {};
@@ -508,17 +572,28 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
         sink(A_TSUR, ts);
       }
 
-
+      // ---- every input of the type has been requested.  The loads above sit in conditional code
+      // (null pointers, the partial-vector path), so in each conditional flux block below the
+      // compiler still counts them as possibly pending and, stores counting in vmcnt like
+      // loads, waits vmcnt(0) at the block's first use of an input: for the stores of the
+      // blocks before it as well.  One wait here, in code that dominates every flux block of
+      // the type, and the blocks need none: the stores issue with the arithmetic.  (TM = 0
+      // keeps the compiler's waits: a full wait here would also retire the next-type prefetch.)
+      if constexpr (TM == 1) {
+        wait_inputs();
+        early();
+      }
       // ---- calc_flux_radiation_blackbody (calc:331-343)
       if ((stages & S_RBBR) && g.rbbr) {
         Vec<C, R> r;
-        if (tp.m_rbbr == FCX_STBO) {
+        if (mt.rbbr == FCX_STBO) {
           FOR_C r.v[i] = rbbr_stbo(ts.v[i]);
           ST(g.rbbr, j0, ns, r);
           sink(A_RBBR, r);
-        } else if (tp.m_rbbr == FCX_ZERO) {
-          ST(g.rbbr, j0, ns, splat<C, R>(R(0)));
-          sink(A_RBBR, splat<C, R>(R(0)));
+        } else if (mt.rbbr == FCX_ZERO) {
+          r = zeros<C, R, TM == 1>();
+          ST(g.rbbr, j0, ns, r);
+          sink(A_RBBR, r);
         }
       }
       // ---- calc_spec_vapor_surface(t) (calc:37-49)
@@ -531,7 +606,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
         const int8_t m = m_me;
         bool have = true;
         if (m == FCX_ZERO) {
-          me = splat<C, R>(R(0));
+          me = zeros<C, R, TM == 1>();
         } else if (m == FCX_CCLM || m == FCX_MOM5) {
           if constexpr (kDerive && VAR == 1) {
             FOR_C me.v[i] = meva_cclm_num(amv.v[i], qa.v[i], qs.v[i], ta.v[i]);
@@ -545,7 +620,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
           have = false;  // none / copy
         }
         if (have) {
-          for (int b = 0; b < tp.bias_adds; ++b) {
+          for (int b = 0; b < mt.bias_adds; ++b) {
             FOR_C me.v[i] = me.v[i] + corr.v[i];
           }
           if (g.meva) ST(g.meva, j0, ns, me);
@@ -555,17 +630,17 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       // ---- calc_flux_heat_latent (calc:135-152)
       if ((stages & S_HLAT) && g.hlat) {
         Vec<C, R> h;
-        if (tp.m_hlat == FCX_WATER) {
+        if (mt.hlat == FCX_WATER) {
           FOR_C h.v[i] = me.v[i] * R(kLv);
           ST(g.hlat, j0, ns, h);
-        } else if (tp.m_hlat == FCX_ICE) {
+        } else if (mt.hlat == FCX_ICE) {
           FOR_C h.v[i] = me.v[i] * R(kLs);
           ST(g.hlat, j0, ns, h);
-        } else if (tp.m_hlat == FCX_ZERO) {
-          h = splat<C, R>(R(0));
+        } else if (mt.hlat == FCX_ZERO) {
+          h = zeros<C, R, TM == 1>();
           ST(g.hlat, j0, ns, h);
         }
-        if (tp.m_hlat == FCX_WATER || tp.m_hlat == FCX_ICE || tp.m_hlat == FCX_ZERO) sink(A_HLAT, h);
+        if (mt.hlat == FCX_WATER || mt.hlat == FCX_ICE || mt.hlat == FCX_ZERO) sink(A_HLAT, h);
       }
       // ---- calc_flux_heat_sensible (calc:167-206), P3: QATM in the q_s slot
       if ((stages & S_HSEN) && g.hsen) {
@@ -585,7 +660,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
           FOR_C h.v[i] = hsen_rco(ta.v[i], ts.v[i], vel.v[i]);
           ST(g.hsen, j0, ns, h);
         } else if (m == FCX_ZERO) {
-          h = splat<C, R>(R(0));
+          h = zeros<C, R, TM == 1>();
           ST(g.hsen, j0, ns, h);
         }
         if (m == FCX_CCLM || m == FCX_MOM5 || m == FCX_RCO || m == FCX_ZERO) sink(A_HSEN, h);
@@ -627,8 +702,8 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       if ((stages & S_RSDR) && g.rsdr) ST(g.rsdr, j0, ns, rsdd);
     }
     if constexpr (!MERGED) {
-      if (j0 < P->n[1]) uv_grid<C, NT, R>(tp, 0, stages, j0, P->n[1], D_);
-      if (j0 < P->n[2]) uv_grid<C, NT, R>(tp, 1, stages, j0, P->n[2], D_);
+      if (j0 < P->n[1]) uv_grid<C, NT, R, TM>(tp, mt, 0, stages, j0, P->n[1], D_);
+      if (j0 < P->n[2]) uv_grid<C, NT, R, TM>(tp, mt, 1, stages, j0, P->n[2], D_);
     }
   }
 #undef HOLD
@@ -975,9 +1050,29 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
       prev_tile = t0 > 0 ? gptr(af.idx)[t0 - 1] : -2;
       next_cont = tend < n && gptr(af.idx)[tend] == gptr(af.idx)[tend - 1];
     }
-    if (j0 < n)
-      process<C, true, VAR, NT, R, TM, RAVG, LdsEmitT<C>, REC, (HALO != 0)>(
-          P, corr_m, j0, emit, AccLds<C, R>{reinterpret_cast<R *>(wp + emit.s), kR}, t0 + kO);
+    // kCompact: the atmosphere cells of the lane's segment starts, a load that depends on the
+    // bit word and the prefix count.  FCX_EARLY_SEG_ATM: issued by process() right behind its
+    // wait for the inputs (word and count have landed with them), so that it flies during the
+    // arithmetic and its wait after the flux pass is a counted one, not a drain of the stores.
+    bool a_loaded = false;
+    auto seg_atm_loads = [&]() {
+      if constexpr (kCompact) {
+        int32_t ord = before + __builtin_popcount(word & ((1u << sh) - 1u));
+#pragma unroll
+        for (int i = 0; i < C; ++i)
+          if (j0 + i < n && ((word >> (sh + i)) & 1u)) a[i] = gptr(af.seg_atm)[ord++];
+        a_loaded = true;
+      }
+    };
+    constexpr bool kEarly = kCompact && TM == 1 && FCX_INPUT_WAIT && FCX_EARLY_SEG_ATM;
+    if (j0 < n) {
+      const AccLds<C, R> acc{reinterpret_cast<R *>(wp + emit.s), kR};
+      if constexpr (kEarly)
+        process<C, true, VAR, NT, R, TM, RAVG, LdsEmitT<C>, REC, (HALO != 0)>(P, corr_m, j0, emit, acc, t0 + kO,
+                                                                             seg_atm_loads);
+      else
+        process<C, true, VAR, NT, R, TM, RAVG, LdsEmitT<C>, REC, (HALO != 0)>(P, corr_m, j0, emit, acc, t0 + kO);
+    }
     if constexpr (kXF) {  // the weights row of the fp32 fluxes (dead cells: weight 0)
 #pragma unroll
       for (int h = 0; h < C / 2; ++h)
@@ -1001,13 +1096,10 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
     bool st[C];
     uint64_t m[C];
     if constexpr (kCompact) {
-      before += __builtin_popcount(word & ((1u << sh) - 1u));
-      int32_t ord = before;
+      if (!a_loaded) seg_atm_loads();
 #pragma unroll
       for (int i = 0; i < C; ++i) {
-        const bool valid = j0 + i < n;
-        st[i] = !valid || ((word >> (sh + i)) & 1u);
-        if (valid && st[i]) a[i] = gptr(af.seg_atm)[ord++];
+        st[i] = !(j0 + i < n) || ((word >> (sh + i)) & 1u);
         m[i] = __ballot(st[i]);
       }
     } else {
