@@ -12,6 +12,7 @@
 #include <atomic>
 #include <cctype>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdarg>
 #include <cstdio>
@@ -76,6 +77,16 @@ struct Buffer {
   bool in_place = false;   // a host array the kernels use through its mapped address
   StageRef st;
   int span = -1;           // fcx_host_malloc array moved by the span transport: its Span
+  // fcx_bind_constant: a namelist-constant input.  No caller array (host stays nullptr and the
+  // buffer is never external), so no transport ever sees it; its mirror in the engine's pools
+  // is filled with cval once at fcx_commit and only ever read.
+  bool constant = false;
+  double cval = 0.0;
+  // decided at fcx_commit: read by the flux pass alone, as a wave-uniform value of the
+  // parameter block (TypeParams::cmask): no device array, no HBM stream (fcx_constant_info 1).
+  // Cleared when a consumer outside the flux pass needs the array (then filled: kind 2).
+  bool uniform = false;
+  bool filled = false;
 };
 
 // The span transport (FCX_OPT_LIB_SPANS) of fcx_host_malloc arrays: one device buffer per
@@ -122,6 +133,7 @@ struct Plan {
   Params host{};
   Params *dev = nullptr;
   std::vector<int> reads, writes;  // buffer ids
+  std::vector<int> const_reads;    // constant buffers the launch streams (never transferred)
   int variant = 0;                 // T=1 specialisation (LaunchConfig::variant)
   bool atm_fused = false;          // exchange -> atmosphere accumulation inside the launch
   AtmosFused af{};
@@ -330,6 +342,8 @@ struct fcx_engine {
   // fcx_plan_check: plans built on the host only (no device memory; bound buffers without a
   // mirror yet stand in with a non-null tag address), audited, and dropped
   bool plan_dry = false;
+  bool const_error = false;   // the last build_plan / constants_check failed over a constant field
+  bool const_uniform = true;  // constants of the flux pass as wave-uniform values (decide_uniform)
   // the span transport of fcx_host_malloc arrays (FCX_OPT_LIB_SPANS, default on)
   bool lib_spans = true;
   std::vector<Span> spans;
@@ -565,6 +579,46 @@ extern "C" int fcx_bind_field(fcx_engine *e, int s, int g, int var, double *ptr,
   }
   e->slot[s][g - 1][var0(var)] = b;
   e->allocated[s][g - 1][var0(var)] = (flags & FCX_ALLOCATED) != 0;
+  return FCX_OK;
+}
+
+extern "C" int fcx_bind_constant(fcx_engine *e, int s, int g, int var, double value) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (e->committed) return fail(FCX_E_STATE, "engine already committed");
+  if (s < 0 || s > kMaxTypes || g < 1 || g > 3 || var < 1 || var > kNumVars)
+    return fail(FCX_E_ARG, "slot (%d,%d,%d) out of range", s, g, var);
+  if (!std::isfinite(value))
+    return fail(FCX_E_ARG, "%s(%d,%s): a constant field needs a finite value", kVarNames[var0(var)], s,
+                g == 1 ? "t" : g == 2 ? "u" : "v");
+  int b = e->buf(s, g, var);
+  if (b < 0) {  // no caller array at all: an own field, like one init_localvar filled
+    Buffer bf;
+    bf.n = e->n[g - 1];
+    b = (int)e->bufs.size();
+    e->bufs.push_back(bf);
+    e->slot[s][g - 1][var0(var)] = b;
+    e->allocated[s][g - 1][var0(var)] = true;
+  }
+  // a bound array: the buffer -- and with it every slot bound to that address -- lets go of it
+  Buffer &bf = e->bufs[(size_t)b];
+  if (!bf.constant) e->by_ptr.erase(bf.external ? bf.dev : bf.host);
+  bf.host = nullptr;
+  if (bf.external) bf.dev = nullptr;
+  bf.external = false;
+  bf.n = std::max(bf.n, e->n[g - 1]);
+  bf.constant = true;
+  bf.cval = value;
+  return FCX_OK;
+}
+
+extern "C" int fcx_constant_info(const fcx_engine *e, int s, int g, int var, int32_t *kind) {
+  if (!e || !kind) return fail(FCX_E_ARG, "NULL argument");
+  if (!e->committed) return fail(FCX_E_STATE, "fcx_commit has not been called");
+  if (s < 0 || s > kMaxTypes || g < 1 || g > 3 || var < 1 || var > kNumVars)
+    return fail(FCX_E_ARG, "slot (%d,%d,%d) out of range", s, g, var);
+  const int b = e->buf(s, g, var);
+  *kind = 0;
+  if (b >= 0 && e->bufs[(size_t)b].constant) *kind = e->bufs[(size_t)b].uniform && !e->bufs[(size_t)b].filled ? 1 : 2;
   return FCX_OK;
 }
 
@@ -947,7 +1001,34 @@ static int ravg_slot(const fcx_engine *e, const Params &P, uint32_t stages, int 
 // nothing; this check, run on every plan before its first launch, names the case where a
 // method the plan computes would need an input the planner did not bind -- the predicates of
 // process() / uv_grid() in fcx_kernels.hip, restated on the parameter block.
-static int plan_audit(const fcx_engine *e, const Params &P) {
+// the mirror of a constant, filled once (stream-ordered before whatever reads it)
+static int fill_constant(fcx_engine *e, Buffer &bf) {
+  if (bf.filled || bf.n <= 0 || !bf.dev) return FCX_OK;
+  const int r = launch_fill(bf.dev, bf.n, bf.cval, e->f32, e->tpad, e->stream);
+  if (r) return fail(FCX_E_HIP, "constant fill launch: %s", hipGetErrorString((hipError_t)r));
+  bf.filled = true;
+  return FCX_OK;
+}
+
+static const double *TGridPtrs::*const kTIn[] = {&TGridPtrs::tsur, &TGridPtrs::fice, &TGridPtrs::psur, &TGridPtrs::patm,
+                                                 &TGridPtrs::qatm, &TGridPtrs::tatm, &TGridPtrs::uatm, &TGridPtrs::vatm,
+                                                 &TGridPtrs::amoi, &TGridPtrs::cmoi, &TGridPtrs::chea};
+static const double *UVGridPtrs::*const kUvIn[] = {&UVGridPtrs::tsur, &UVGridPtrs::fice, &UVGridPtrs::psur, &UVGridPtrs::uatm,
+                                                   &UVGridPtrs::vatm, &UVGridPtrs::amom, &UVGridPtrs::cmom};
+static_assert(sizeof kTIn / sizeof kTIn[0] == kUvBit0 && sizeof kUvIn / sizeof kUvIn[0] == kUvBits, "ConstBit order");
+
+static int plan_audit(const fcx_engine *e, const Params &P0) {
+  // a wave-uniform input is bound whatever its bits (0.0 is all zeros): audited as a non-null tag
+  Params P = P0;
+  static const double kTag = 0.0;
+  for (int s = 0; s < P.num_types; ++s) {
+    TypeParams &tp = P.type[s];
+    for (int b = 0; b < kUvBit0; ++b)
+      if ((tp.cmask >> b) & 1u) tp.t.*kTIn[b] = &kTag;
+    for (int k = 0; k < 2; ++k)
+      for (int b = 0; b < kUvBits; ++b)
+        if ((tp.cmask >> (kUvBit0 + kUvBits * k + b)) & 1u) tp.uv[k].*kUvIn[b] = &kTag;
+  }
   const uint32_t st = P.stages;
   if (P.n_max <= 0) return FCX_OK;  // nothing is launched (a rank with an empty task)
   auto need = [&](const void *ptr, int s, const char *what, const char *name) -> int {
@@ -1070,7 +1151,8 @@ static int plan_audit(const fcx_engine *e, const Params &P) {
 static int build_plan(fcx_engine *e, uint32_t stages, int avg_phases, Plan &pl) {
   Params &P = pl.host;
   std::memset(&P, 0, sizeof P);
-  std::set<int> reads, writes;
+  std::set<int> reads, writes, const_reads;
+  std::string const_written;  // the first constant field this plan would write
   for (int g = 0; g < 3; ++g) P.n[g] = e->n[g];
   P.tpad = e->tpad;
   P.num_types = e->T;
@@ -1094,12 +1176,19 @@ static int build_plan(fcx_engine *e, uint32_t stages, int avg_phases, Plan &pl) 
     const int b = e->buf(s, g, var);
     if (b < 0) return nullptr;
     if (e->plan_dry && unbind && std::strcmp(unbind, kVarNames[var0(var)]) == 0) return nullptr;
-    reads.insert(b);
+    // a constant is read from its filled mirror: never uploaded, staged, spanned or mapped
+    (e->bufs[(size_t)b].constant ? const_reads : reads).insert(b);
     return dev_of(b);
   };
   auto out = [&](int s, int g, int var) -> double * {
     const int b = e->buf(s, g, var);
     if (b < 0) return nullptr;
+    if (e->bufs[(size_t)b].constant && const_written.empty()) {
+      char msg[160];
+      snprintf(msg, sizeof msg, "constant field %s(%d,%s) would be written (stages 0x%x): a namelist constant is an input",
+               kVarNames[var0(var)], s, g == 1 ? "t" : g == 2 ? "u" : "v", (unsigned)stages);
+      const_written = msg;
+    }
     writes.insert(b);
     return dev_of(b);
   };
@@ -1283,13 +1372,47 @@ static int build_plan(fcx_engine *e, uint32_t stages, int avg_phases, Plan &pl) 
                       kVarNames[var0(var)], s, kVarNames[var0(var)]);
         // values produced in this launch are re-read by the same thread (in order)
         ae.x[s - 1] = dev_of(e->buf(s, g, var));
-        if (!writes.count(e->buf(s, g, var))) reads.insert(e->buf(s, g, var));
+        if (!writes.count(e->buf(s, g, var)))
+          (e->bufs[(size_t)e->buf(s, g, var)].constant ? const_reads : reads).insert(e->buf(s, g, var));
         ae.fare[s - 1] = in(s, g, FCX_FARE);
       }
       n_max = std::max(n_max, e->n[g - 1]);
     }
   }
+  // Wave-uniform constants (TypeParams::cmask).  The kernel families that take them without
+  // spilling, losing a wave per SIMD or slowing the step (profiles/r10/):
+  // fp64 launches of the generic and the CCLM kernels without register averages.  There a uniform
+  // constant (decide_uniform) goes into the parameter block as its value and leaves the plan's
+  // streamed set; in the other families the launch streams its filled mirror.
+  // (the launch's template arguments: plan_launch takes variant 0 when specialisation is off,
+  // and a plan with register averages always runs the register-average kernels)
+  if (uniform_family(e->f32, e->specialize ? pl.variant : 0, P.ravg_on != 0)) {
+    static const int kTVar[] = {FCX_TSUR, FCX_FICE, FCX_PSUR, FCX_PATM, FCX_QATM, FCX_TATM,
+                                FCX_UATM, FCX_VATM, FCX_AMOI, FCX_CMOI, FCX_CHEA};
+    static const int kUvVar[] = {FCX_TSUR, FCX_FICE, FCX_PSUR, FCX_UATM, FCX_VATM, FCX_AMOM, FCX_CMOM};
+    auto value = [&](const double *&member, uint32_t &mask, int bit, int s, int g, int var) {
+      const int b = e->buf(s, g, var);
+      if (!member || b < 0 || !e->bufs[(size_t)b].uniform) return;
+      uint64_t w;
+      std::memcpy(&w, &e->bufs[(size_t)b].cval, sizeof w);
+      member = reinterpret_cast<const double *>((uintptr_t)w);
+      mask |= 1u << bit;
+      const_reads.erase(b);
+    };
+    for (int s = 1; s <= e->T; ++s) {
+      TypeParams &tp = P.type[s - 1];
+      for (int b = 0; b < kUvBit0; ++b) value(tp.t.*kTIn[b], tp.cmask, b, s, 1, kTVar[b]);
+      for (int k = 0; k < 2; ++k)
+        for (int b = 0; b < kUvBits; ++b)
+          value(tp.uv[k].*kUvIn[b], tp.cmask, kUvBit0 + kUvBits * k + b, s, 2 + k, kUvVar[b]);
+    }
+  }
   P.n_max = n_max;
+  if (!const_written.empty()) {
+    e->const_error = true;
+    return fail(FCX_E_STATE, "%s", const_written.c_str());
+  }
+  pl.const_reads.assign(const_reads.begin(), const_reads.end());
   pl.reads.assign(reads.begin(), reads.end());
   pl.writes.assign(writes.begin(), writes.end());
   // buffers that are both read and written in the launch are produced there: not inputs
@@ -1299,6 +1422,8 @@ static int build_plan(fcx_engine *e, uint32_t stages, int avg_phases, Plan &pl) 
   pl.reads.swap(pure);
   if (int r = plan_audit(e, P)) return r;
   if (e->plan_dry) return FCX_OK;  // fcx_plan_check: host only
+  for (int b : pl.const_reads)  // the first plan that streams a constant fills its mirror
+    if (int r = fill_constant(e, e->bufs[(size_t)b])) return r;
   plan_fused_atmos(e, pl, stages, avg_phases);
   if (int r = plan_fused_records(e, pl, stages, avg_phases)) return r;
   HIP_TRY(hipMalloc(&pl.dev, sizeof(Params)));
@@ -1312,10 +1437,75 @@ static int staged_sequence(int phase, std::vector<std::pair<uint32_t, int>> &seq
 // Every plan the engine can launch, built on the host and audited (plan_audit), before
 // fcx_commit and without a GPU: the whole phases with their averages, the reference
 // sequence of a regridding engine, each per-call subroutine and each explicit average.
+// Which constants the flux pass takes as wave-uniform values (Buffer::uniform): every slot bound
+// to the buffer is one of the kernel inputs of TGridPtrs / UVGridPtrs, and nothing outside the
+// flux pass reads it -- not a regrid source, not a field of an average, not accumulated to the
+// atmosphere or remapped.  Those consumers read arrays: such a constant keeps its filled mirror.
+static void decide_uniform(fcx_engine *e) {
+  static const int kIn[] = {FCX_TSUR, FCX_FICE, FCX_PSUR, FCX_PATM, FCX_QATM, FCX_TATM, FCX_UATM,
+                            FCX_VATM, FCX_AMOI, FCX_CMOI, FCX_CHEA, FCX_AMOM, FCX_CMOM};
+  for (auto &bf : e->bufs) bf.uniform = bf.constant && e->const_uniform;
+  auto array = [&](int s, int g, int v) {
+    const int b = e->buf(s, g, v);
+    if (b >= 0) e->bufs[(size_t)b].uniform = false;
+  };
+  for (int s = 0; s <= kMaxTypes; ++s)
+    for (int g = 1; g <= 3; ++g)
+      for (int v = 1; v <= kNumVars; ++v) {
+        const bool in = std::find(std::begin(kIn), std::end(kIn), v) != std::end(kIn);
+        bool avg = false;
+        for (auto &a : e->averages) avg = avg || a.second.second == v;
+        if (!in || avg || e->put_to[s][g - 1][v - 1]) array(s, g, v);
+      }
+  for (auto &f : e->atm_fields) array(f.s, f.g, f.var);
+  for (auto &rm : e->remaps)
+    for (auto &f : rm.fields) array(f.s, f.g, f.var);
+}
+
+// A constant field is an input: the slots a method or a regridding writes without any plan
+// naming them as outputs ('copy' targets alias the type-1 array, prepare:36-38; regrid
+// destinations, basic:463-522) must not be constants either.
+static int constants_check(const fcx_engine *e) {
+  auto is_const = [&](int s, int g, int var) {
+    const int b = e->buf(s, g, var);
+    return b >= 0 && e->bufs[(size_t)b].constant;
+  };
+  auto gname = [](int g) { return g == 1 ? "t" : g == 2 ? "u" : "v"; };
+  static const struct {
+    int flux, g, var;
+  } kCopy[] = {{FCX_SPEC_VAPOR_SURFACE_T, 1, FCX_QSUR}, {FCX_SPEC_VAPOR_SURFACE_T + 1, 2, FCX_QSUR},
+               {FCX_SPEC_VAPOR_SURFACE_T + 2, 3, FCX_QSUR}, {FCX_FLUX_MASS_EVAP, 1, FCX_MEVA},
+               {FCX_FLUX_HEAT_LATENT, 1, FCX_HLAT}, {FCX_FLUX_HEAT_SENSIBLE, 1, FCX_HSEN},
+               {FCX_FLUX_MOMENTUM, 2, FCX_UMOM}, {FCX_FLUX_MOMENTUM, 3, FCX_VMOM},
+               {FCX_FLUX_RADIATION_BLACKBODY, 1, FCX_RBBR}};
+  for (int s = 1; s <= e->T; ++s)
+    for (auto &c : kCopy)
+      if (e->method[c.flux][s - 1] == FCX_COPY && is_const(s, c.g, c.var))
+        return fail(FCX_E_STATE, "constant field %s(%d,%s) is the target of a 'copy' method: a namelist constant is an input",
+                    kVarNames[var0(c.var)], s, gname(c.g));
+  for (int s = 0; s <= kMaxTypes; ++s)
+    for (int g = 1; g <= 3; ++g)
+      for (int v = 1; v <= kNumVars; ++v)
+        for (int k = 0; k < 3; ++k)
+          if (((e->put_to[s][g - 1][v - 1] >> k) & 1) && k + 1 != g && is_const(s, k + 1, v))
+            return fail(FCX_E_STATE, "constant field %s(%d,%s) is a regridding destination: a namelist constant is an input",
+                        kVarNames[v - 1], s, gname(k + 1));
+  return FCX_OK;
+}
+
+static int plan_check_all(fcx_engine *e, bool constants_only = false);
 extern "C" int fcx_plan_check(fcx_engine *e) {
   if (!e) return fail(FCX_E_ARG, "NULL engine");
   if (e->committed) return fail(FCX_E_STATE, "fcx_plan_check runs before fcx_commit");
   if (int r = validate(e)) return r;
+  decide_uniform(e);
+  return plan_check_all(e);
+}
+
+// constants_only (fcx_commit of an engine with constants): only the errors that name a constant
+// field count; every other finding is left to the run that builds the plan, as without constants
+static int plan_check_all(fcx_engine *e, bool constants_only) {
+  if (int r = constants_check(e)) return r;
   std::vector<std::pair<uint32_t, int>> sets;
   for (int ph : {(int)FCX_PHASE_EARLY, (int)FCX_PHASE_NORMAL, (int)(FCX_PHASE_EARLY | FCX_PHASE_NORMAL)}) {
     sets.push_back({phase_stages(ph), ph});
@@ -1331,7 +1521,12 @@ extern "C" int fcx_plan_check(fcx_engine *e) {
   int rc = FCX_OK;
   for (auto &x : sets) {
     Plan p;
-    if ((rc = build_plan(e, x.first, x.second, p)) != FCX_OK) break;
+    const std::string saved = g_err;
+    e->const_error = false;
+    if ((rc = build_plan(e, x.first, x.second, p)) == FCX_OK) continue;
+    if (!constants_only || e->const_error) break;
+    rc = FCX_OK;
+    g_err = saved;
   }
   e->plan_dry = false;
   return rc;
@@ -1671,6 +1866,10 @@ static int alloc_tiled(fcx_engine *e) {
     if (build_plan(e, phase_stages(FCX_PHASE_EARLY | FCX_PHASE_NORMAL), FCX_PHASE_EARLY | FCX_PHASE_NORMAL, p) ==
         FCX_OK) {
       for (int b : p.reads) cls[b] = kRead;
+      // a constant the launch streams sits with the arrays it reads, so that a wave finds every
+      // input stream in one region: the last slots of the read pool, behind the transferred ones,
+      // which stay one run
+      for (int b : p.const_reads) cls[b] = kRead;
       for (int b : p.writes) cls[b] = kWrite;
     }
     e->plan_dry = false;
@@ -1697,7 +1896,11 @@ static int alloc_tiled(fcx_engine *e) {
   // pool and slot of every buffer: read pool, write pool, then the cold ones S to a pool
   std::vector<std::pair<int, int>> at(e->bufs.size());
   int npools = 0, fill[3] = {0, 0, 0}, pool_of[2] = {-1, -1}, cold_pool = -1;
-  for (size_t b = 0; b < e->bufs.size(); ++b) {
+  std::vector<size_t> order;  // the constants after the arrays
+  for (int pass = 0; pass < 2; ++pass)
+    for (size_t b = 0; b < e->bufs.size(); ++b)
+      if (e->bufs[b].constant == (pass == 1)) order.push_back(b);
+  for (size_t b : order) {
     const int c = cls[b];
     if (c != kCold) {
       if (pool_of[c] < 0) pool_of[c] = npools++;
@@ -2203,6 +2406,11 @@ extern "C" int fcx_commit(fcx_engine *e) {
   if (!e) return fail(FCX_E_ARG, "NULL engine");
   if (e->committed) return FCX_OK;
   if (int r = validate(e)) return r;
+  bool any_constant = false;
+  for (auto &bf : e->bufs) any_constant = any_constant || bf.constant;
+  decide_uniform(e);
+  if (any_constant)  // a constant some plan would write is an error here, not at that plan's first run
+    if (int r = plan_check_all(e, true)) return r;
   if (int r = gpu_init(e)) return r;
   // Zero-copy of fcx_host_malloc arrays.  2 (auto, default): where the pipelined step would
   // not apply (grids below two chunks, where the step is latency-bound and per-array copies
@@ -2248,6 +2456,14 @@ extern "C" int fcx_commit(fcx_engine *e) {
     for (size_t b = 0; b < e->bufs.size(); ++b)
       if (!e->bufs[b].external) e->bufs[b].dev = reinterpret_cast<double *>((char *)e->pool + off[b]);
   }
+  // the constants' mirrors: filled once, in the mirrors' layout, and only read from here on
+  for (auto &bf : e->bufs) {
+    // read outside the flux pass (a regrid source, an averaged, accumulated or remapped field):
+    // filled now; a uniform one when a plan streams it or fcx_device_ptr asks for it
+    if (!bf.constant || bf.uniform) continue;
+    if (int r = fill_constant(e, bf)) return r;
+  }
+  if (any_constant) HIP_TRY(hipStreamSynchronize(e->stream));
   if (e->lcorr) {
     HIP_TRY(hipMalloc(&e->corr_dev, std::max<size_t>(e->corr_mm.size(), 1) * e->esize));
     if (e->f32) {  // rounded once; the fp32 kernels add them in fp32
@@ -2496,7 +2712,7 @@ static int copy_bufs(fcx_engine *e, const std::vector<int> &ids, bool h2d, std::
   bool direct = false;
   for (int b : ids) {
     const Buffer &bf = e->bufs[b];
-    if (bf.n == 0) continue;
+    if (bf.n == 0 || bf.constant) continue;
     if (h2d && (size_t)b < e->field_sent.size() && e->field_sent[(size_t)b]) continue;  // fcx_upload_field
     if (bf.st.sp >= 0) {  // (also a heap array whose mirror is a mapped arena image)
       xs.push_back(xfer_of(bf.st, bf.host, bf.n));
@@ -2738,6 +2954,7 @@ extern "C" int fcx_upload_field(fcx_engine *e, int s, int g, int var) {
     return fail(FCX_E_ARG, "field (%d, %d, %d) outside the data model", s, g, var);
   const int b = e->buf(s, g, var);
   if (b < 0) return fail(FCX_E_ARG, "local_field(%d,%d)%%var(%s) is not bound", s, g, kVarNames[var - 1]);
+  if (e->bufs[(size_t)b].constant) return FCX_OK;  // nothing to hand over: the engine filled it at commit
   if (e->field_sent.size() != e->bufs.size()) e->field_sent.assign(e->bufs.size(), 0);
   if (e->field_sent[(size_t)b]) return FCX_OK;  // an alias of a field already handed over
   e->field_sent[(size_t)b] = 1;
@@ -3409,6 +3626,12 @@ extern "C" int fcx_device_ptr(fcx_engine *e, int s, int g, int var, double **dpt
   if (int r = check(e)) return r;
   if (!dptr || s < 0 || s > kMaxTypes || g < 1 || g > 3 || var < 1 || var > kNumVars)
     return fail(FCX_E_ARG, "bad arguments");
+  const int b = e->buf(s, g, var);
+  if (b >= 0 && e->bufs[(size_t)b].constant && !e->bufs[(size_t)b].filled && e->bufs[(size_t)b].n > 0) {
+    // a uniform constant asked for as an array: its mirror is filled now (the plans keep the value)
+    if (int r = fill_constant(e, e->bufs[(size_t)b])) return r;
+    HIP_TRY(hipStreamSynchronize(e->stream));
+  }
   *dptr = e->dptr(s, g, var);
   return FCX_OK;
 }
@@ -3485,6 +3708,7 @@ extern "C" int fcx_algorithmic_bytes(fcx_engine *e, int phase, int64_t *bytes) {
   if (int r = get_plan(e, phase_stages(phase), phase, &pl)) return r;
   int64_t b = 0;
   for (int id : pl->reads) b += e->bufs[id].n;
+  for (int id : pl->const_reads) b += e->bufs[id].n;  // streamed from their filled mirrors
   for (int id : pl->writes) b += e->bufs[id].n;
   if (e->lcorr && (phase & FCX_PHASE_NORMAL)) b += e->n[0];
   int64_t extra = 0;  // atmosphere accumulation: weights (+cols), re-read fields, outputs

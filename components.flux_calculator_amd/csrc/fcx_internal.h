@@ -96,8 +96,30 @@ struct TypeParams {
   UVGridPtrs uv[2];
   int8_t m_qsur[3], m_meva, m_hlat, m_hsen, m_mom, m_rbbr;
   int8_t bias_adds;  // how many times corr(month) is added to MEVA (1 + #'copy' aliases)
-  int8_t pad[7];
+  int8_t pad[3];
+  // Wave-uniform inputs (fcx_bind_constant): bit ConstBit of an input of t / uv[0] / uv[1] set =
+  // that member's 8 bytes hold the VALUE (the double's bits; in an fp32 engine the float's bits
+  // in the low word), not an address, and the flux pass issues no vector load for it.  The
+  // high half of the bias_adds word, so it arrives with the same scalar load.
+  uint32_t cmask;
 };
+enum ConstBit : int {  // TGridPtrs inputs 0..10, UVGridPtrs inputs of uv[k] at kUvBit0 + 7 k
+  K_TSUR = 0, K_FICE, K_PSUR, K_PATM, K_QATM, K_TATM, K_UATM, K_VATM, K_AMOI, K_CMOI, K_CHEA,
+  kUvBit0 = 11, KU_TSUR = 0, KU_FICE, KU_PSUR, KU_UATM, KU_VATM, KU_AMOM, KU_CMOM, kUvBits = 7
+};
+static_assert(kUvBit0 + 2 * kUvBits <= 32, "TypeParams::cmask: 25 bits");
+// the wave-uniform inputs in the kernels (A/B builds: 0 = every input is an array)
+#ifndef FCX_CONST_UNIFORM
+#define FCX_CONST_UNIFORM 1
+#endif
+// Which kernel family takes wave-uniform inputs -- ONE rule for the kernels (uniform_inputs<>,
+// the template arguments of process) and for the planner (build_plan, with the variant and
+// register-average mode its launch will be instantiated with): a set cmask bit in a launch of
+// any other family would be a value's bits read as an address.  fp64 generic (variant 0) and
+// CCLM (1) kernels without register averages; why not the others: DESIGN.md section 3.
+constexpr bool uniform_family(bool f32, int variant, bool ravg) {
+  return FCX_CONST_UNIFORM && !f32 && !ravg && (variant == 0 || variant == 1);
+}
 // The kernels read a type's method bytes as ONE aligned 64-bit word (m_qsur[0] in the low
 // byte ... m_rbbr in the high one) and bias_adds with its padding as the next 64-bit word
 // (fcx_kernels.hip, type_methods): wave-uniform scalar loads, where a byte member is a
@@ -111,6 +133,8 @@ static_assert(offsetof(TypeParams, m_qsur) % 8 == 0 && offsetof(TypeParams, m_me
 static_assert(offsetof(TypeParams, bias_adds) == offsetof(TypeParams, m_qsur) + 8 &&
                   sizeof(TypeParams) == offsetof(TypeParams, bias_adds) + 8,
               "TypeParams: bias_adds and its padding are the next aligned 64-bit word");
+static_assert(offsetof(TypeParams, cmask) == offsetof(TypeParams, bias_adds) + 4,
+              "TypeParams: cmask is the high half of the bias_adds word");
 static_assert(sizeof(TypeParams) % 8 == 0 && alignof(TypeParams) == 8, "TypeParams: 8-B aligned in Params::type[]");
 // type-0 average: X0 = sum_{s=1..T} X_s * FARE_s, in order (calc:376-383)
 struct AvgEntry {
@@ -356,6 +380,9 @@ int launch_atmos_finish(const AtmosArgs &a, int32_t n_boundaries, void *stream);
 int launch_regrid_csr(const int32_t *row_ptr, const int32_t *col, const double *w,
                       const double *src, double *dst, int64_t n_dst, void *stream, bool f32 = false,
                       int64_t tpad = 0);
-int launch_zero(double *x, int64_t n, void *stream);
+// x[tiled(j, tpad)] = value for the cells j < n of an engine buffer in the layout tpad (the
+// mirror of a constant field, fcx_bind_constant); f32: x is a float array and value is
+// rounded to float once
+int launch_fill(double *x, int64_t n, double value, bool f32, int64_t tpad, void *stream);
 
 }  // namespace fcx

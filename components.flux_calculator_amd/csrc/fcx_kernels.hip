@@ -143,7 +143,9 @@ __device__ __forceinline__ Vec<C, R> zeros() {
 struct Methods {
   int8_t qsur[3], meva, hlat, hsen, mom, rbbr;
   int8_t bias_adds;
+  uint32_t cmask;  // TypeParams::cmask: which inputs are wave-uniform values
 };
+
 // The parameter block is not written while a launch runs, so its words may be read in the
 // constant address space: a uniform load there is a scalar load whatever the compiler can
 // prove about the stores around it.  (Read as global memory, the same words came back as
@@ -160,8 +162,45 @@ __device__ __forceinline__ int8_t byte_of(uint64_t w, int k) { return (int8_t)(u
 __device__ __forceinline__ Methods type_methods(const TypeParams &tp) {
   const uint64_t w = *cptr(&tp.m_qsur[0]), b = *cptr(&tp.bias_adds);
   return Methods{{byte_of(w, 0), byte_of(w, 1), byte_of(w, 2)}, byte_of(w, 3), byte_of(w, 4),
-                 byte_of(w, 5),  byte_of(w, 6), byte_of(w, 7),  byte_of(b, 0)};
+                 byte_of(w, 5),  byte_of(w, 6), byte_of(w, 7),  byte_of(b, 0),
+                 FCX_CONST_UNIFORM ? (uint32_t)(b >> 32) : 0u};
 }
+__device__ __forceinline__ uint32_t type_cmask(const TypeParams &tp) {
+  return FCX_CONST_UNIFORM ? (uint32_t)(*cptr(&tp.bias_adds) >> 32) : 0u;
+}
+// An input that may be a wave-uniform value (TypeParams::cmask): c set = the member's bytes are
+// the value, splat from the scalar registers, no vector load.  Lanes at or past n get 1 like
+// ld()'s partial vector, so a constant differs from an array holding the value in nothing but
+// the load, dead lanes included.
+template <int C, bool NT, class R>
+__device__ __forceinline__ Vec<C, R> ldu(const double *p, bool c, int64_t j0, int64_t n, int64_t D_) {
+  if (c) {
+    const uint64_t w = (uint64_t) reinterpret_cast<uintptr_t>(p);
+    R v;
+    if constexpr (sizeof(R) == 8)
+      v = __builtin_bit_cast(double, w);
+    else
+      v = __builtin_bit_cast(float, (uint32_t)w);
+    Vec<C, R> r;
+#pragma unroll
+    for (int i = 0; i < C; ++i) r.v[i] = (j0 + i < n) ? v : R(1);
+    return r;
+  }
+  return ld<C, NT, R>(reinterpret_cast<const R *>(p) + D_, j0, n);
+}
+#define LDU(p, c, j, n) ldu<C, NT, R>(p, c, j, n, D_)
+// The instantiations that take wave-uniform inputs: the fp64 generic and CCLM kernels without
+// register averages.  In the fp32 kernels and the MOM5 and RCO kernels the uniform path cost
+// scratch or a wave per SIMD when it was compiled in (DESIGN.md section 3,
+// profiles/r10/isa/registers_uniform_everywhere.txt); in the register-average kernels it fit
+// the registers but the T = 2 bench step lost 2.6 % with it (profiles/r10/pairs/
+// t2_uniform_in_ravg_kernels.txt).  There the mask is a compile-time zero and the planner
+// binds a constant's filled mirror instead (fcx_engine.hip, build_plan: the same rule).
+template <class R, int VAR, bool RAVG>
+constexpr bool uniform_inputs() {
+  return uniform_family(sizeof(R) == 4, VAR, RAVG);  // (fcx_internal.h: the planner's rule too)
+}
+__device__ __forceinline__ bool cbit(uint32_t m, int bit) { return (m >> bit) & 1u; }
 // The wait of the single-type kernels for a type's inputs: vmcnt(0) alone (expcnt and lgkmcnt
 // left at their maxima), as a builtin so that the compiler's wait-count pass sees it.
 __device__ __forceinline__ void wait_inputs() {
@@ -223,7 +262,7 @@ __device__ __forceinline__ void momentum(int8_t m, bool north, const UVGridPtrs 
 
 // QSUR + momentum on one separate u or v grid (non-merged layout).
 // TM = 1: one wait for the grid's inputs before its first store (process, wait_inputs).
-template <int C, bool NT, class R, int TM>
+template <int C, bool NT, class R, int TM, bool UNI>
 __device__ __forceinline__ void uv_grid(const TypeParams &tp, const Methods &mt, int k, uint32_t stages, int64_t j0,
                                         int64_t n, int64_t D_) {
   const UVGridPtrs &g = tp.uv[k];
@@ -233,17 +272,18 @@ __device__ __forceinline__ void uv_grid(const TypeParams &tp, const Methods &mt,
   const bool do_m = (stages & s_mom) && g.mom;
   if (!do_q && !do_m) return;
   Vec<C, R> ts = {}, fi = {}, ps = {}, u = {}, v = {}, a = {}, qs = {};
-  if (g.tsur) ts = LD(g.tsur, j0, n);
-  if (g.psur) ps = LD(g.psur, j0, n);
+  const uint32_t cm = UNI ? mt.cmask >> (kUvBit0 + kUvBits * k) : 0u;  // this grid's bits
+  if (g.tsur || cbit(cm, KU_TSUR)) ts = LDU(g.tsur, cbit(cm, KU_TSUR), j0, n);
+  if (g.psur || cbit(cm, KU_PSUR)) ps = LDU(g.psur, cbit(cm, KU_PSUR), j0, n);
   // every load is guarded by its own pointer, whatever the method says: a method whose input
   // the planner left unbound reads nothing (plan_audit at plan build names that case as an
   // error before any launch; round-5 fault: 'zero' momentum loaded unbound winds)
-  if (do_q && g.fice) fi = LD(g.fice, j0, n);
+  if (do_q && (g.fice || cbit(cm, KU_FICE))) fi = LDU(g.fice, cbit(cm, KU_FICE), j0, n);
   if (do_m) {  // ('zero' momentum binds no wind: the planner leaves uatm / vatm unset)
-    if (g.uatm) u = LD(g.uatm, j0, n);
-    if (g.vatm) v = LD(g.vatm, j0, n);
-    if (mt.mom == FCX_CCLM && g.amom) a = LD(g.amom, j0, n);
-    if (mt.mom == FCX_MOM5 && g.cmom) a = LD(g.cmom, j0, n);
+    if (g.uatm || cbit(cm, KU_UATM)) u = LDU(g.uatm, cbit(cm, KU_UATM), j0, n);
+    if (g.vatm || cbit(cm, KU_VATM)) v = LDU(g.vatm, cbit(cm, KU_VATM), j0, n);
+    if (mt.mom == FCX_CCLM && (g.amom || cbit(cm, KU_AMOM))) a = LDU(g.amom, cbit(cm, KU_AMOM), j0, n);
+    if (mt.mom == FCX_MOM5 && (g.cmom || cbit(cm, KU_CMOM))) a = LDU(g.cmom, cbit(cm, KU_CMOM), j0, n);
     if (g.qsur_in && !do_q) qs = LD(g.qsur_in, j0, n);
   }
   if constexpr (TM == 1) wait_inputs();
@@ -428,18 +468,32 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
   // 6-7 % per step.  Holding every input (round 1) kept ~56 VGPRs live and lost.
   constexpr bool kReload = TM == 0;  // bottom-side inputs: loaded per type
   // grp.member names the pointer in TypeParams.  ATM: an atmosphere-side input (held).
-#define HOLDX(var, grp, member, ATM)                  \
+  // A held input is the pair (member bytes, constant bit): an array and a constant never compare
+  // equal even where a value's bits look like an address, and two constants differ by their
+  // bits.  h_cm holds the constant bits of the held inputs (wave-uniform, scalar registers).
+  constexpr bool kUni = uniform_inputs<R, VAR, RAVG>();
+  uint32_t h_cm = 0, cm = 0;  // cm: the current type's TypeParams::cmask
+  auto is_new = [&](const double *ptr_, const double *held, int bit) {
+    if constexpr (!kUni) return ptr_ && ptr_ != held;
+    const bool c_ = cbit(cm, bit);
+    return (ptr_ || c_) && (ptr_ != held || c_ != cbit(h_cm, bit));
+  };
+  auto hold = [&](int bit) {
+    if constexpr (kUni) h_cm = (h_cm & ~(1u << bit)) | ((uint32_t)cbit(cm, bit) << bit);
+  };
+#define HOLDX(var, grp, member, ATM, bit)             \
   {                                                   \
     const double *ptr_ = tp.grp.member;               \
     if constexpr (kReload && !ATM) {                  \
-      if (ptr_) var = LD(ptr_, j0, nt);               \
-    } else if (ptr_ && ptr_ != h_##var) {             \
-      var = LD(ptr_, j0, nt);                         \
+      if (ptr_ || cbit(cm, bit)) var = LDU(ptr_, cbit(cm, bit), j0, nt); \
+    } else if (is_new(ptr_, h_##var, bit)) {          \
+      var = LDU(ptr_, cbit(cm, bit), j0, nt);         \
       h_##var = ptr_;                                 \
+      hold(bit);                                      \
     }                                                 \
   }
-#define HOLD(var, grp, member) HOLDX(var, grp, member, false)
-#define HOLDA(var, grp, member) HOLDX(var, grp, member, true)
+#define HOLD(var, grp, member, bit) HOLDX(var, grp, member, false, bit)
+#define HOLDA(var, grp, member, bit) HOLDX(var, grp, member, true, bit)
   // Next-type prefetch (multi-type kernels): the bottom-side inputs of type s+1 (TSUR FICE
   // CMOI CHEA CMOM and the FARE of the averages) are loaded when type s starts, so that the
   // wave does not stall on memory between two types.  The fused T = 2 kernels then hold
@@ -464,12 +518,13 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
   Vec<C, R> n_ts = {}, n_fi = {}, n_cmoi = {}, n_chea = {}, n_cmom = {}, n_fare = {};
   auto prefetch = [&](int s2) {
     const TypeParams &q = P->type[s2];
-    if (q.t.tsur) n_ts = LD(q.t.tsur, j0, nt);
-    if (q.t.fice) n_fi = LD(q.t.fice, j0, nt);
-    if (q.t.cmoi) n_cmoi = LD(q.t.cmoi, j0, nt);
-    if (q.t.chea) n_chea = LD(q.t.chea, j0, nt);
+    const uint32_t qm = kUni ? type_cmask(q) : 0u;
+    if (q.t.tsur || cbit(qm, K_TSUR)) n_ts = LDU(q.t.tsur, cbit(qm, K_TSUR), j0, nt);
+    if (q.t.fice || cbit(qm, K_FICE)) n_fi = LDU(q.t.fice, cbit(qm, K_FICE), j0, nt);
+    if (q.t.cmoi || cbit(qm, K_CMOI)) n_cmoi = LDU(q.t.cmoi, cbit(qm, K_CMOI), j0, nt);
+    if (q.t.chea || cbit(qm, K_CHEA)) n_chea = LDU(q.t.chea, cbit(qm, K_CHEA), j0, nt);
     if constexpr (MERGED) {
-      if (q.uv[0].cmom) n_cmom = LD(q.uv[0].cmom, j0, nt);
+      if (q.uv[0].cmom || cbit(qm, kUvBit0 + KU_CMOM)) n_cmom = LDU(q.uv[0].cmom, cbit(qm, kUvBit0 + KU_CMOM), j0, nt);
     }
     if constexpr (RAVG) {
       if (P->ravg_on && P->ravg.fare[s2]) n_fare = LD(P->ravg.fare[s2], j0, nt);
@@ -486,6 +541,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
     const TypeParams &tp = P->type[s];
     const TGridPtrs &g = tp.t;
     const Methods mt = type_methods(tp);
+    cm = kUni ? mt.cmask : 0u;
     constexpr int8_t kVarMethod = VAR == 1 ? FCX_CCLM : VAR == 2 ? FCX_MOM5 : FCX_RCO;
     const int8_t m_q = VAR ? (VAR == 3 ? FCX_NONE : FCX_CCLM) : mt.qsur[0];
     const int8_t m_qu = VAR ? m_q : mt.qsur[1];
@@ -505,32 +561,33 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
         if constexpr (RAVG) sink.fare = n_fare;
         if (s + 1 < T) prefetch(s + 1);
       } else {
-        HOLD(ts, t, tsur)
-        HOLD(fi, t, fice)
+        HOLD(ts, t, tsur, K_TSUR)
+        HOLD(fi, t, fice, K_FICE)
       }
       // which derived atmosphere terms this type must (re)form: its fields differ from the held ones
-      const bool wind_new = (g.uatm && g.uatm != h_u) || (g.vatm && g.vatm != h_v);
+      const bool wind_new = is_new(g.uatm, h_u, K_UATM) || is_new(g.vatm, h_v, K_VATM);
       bool d_ef = false, d_amv = false, d_mvp = false;
       if constexpr (kDerive) {
-        const bool ps_new = g.psur && g.psur != h_ps;
-        d_ef = ps_new || (g.patm && g.patm != h_pa) || (g.tatm && g.tatm != h_ta);
+        const bool ps_new = is_new(g.psur, h_ps, K_PSUR);
+        d_ef = ps_new || is_new(g.patm, h_pa, K_PATM) || is_new(g.tatm, h_ta, K_TATM);
         if constexpr (VAR == 1) {
-          d_amv = ps_new || wind_new || (g.amoi && g.amoi != h_amoi);
-          d_mvp = ps_new || wind_new || (tp.uv[0].amom && tp.uv[0].amom != h_amom);
+          d_amv = ps_new || wind_new || is_new(g.amoi, h_amoi, K_AMOI);
+          d_mvp = ps_new || wind_new || is_new(tp.uv[0].amom, h_amom, kUvBit0 + KU_AMOM);
         }
       }
-      HOLDA(ps, t, psur)
-      if constexpr (!kDerive) HOLDA(pa, t, patm)
-      HOLDA(qa, t, qatm)
-      HOLDA(ta, t, tatm)
-      HOLDA(u, t, uatm)
-      HOLDA(v, t, vatm)
-      if constexpr (!(kDerive && VAR == 1)) HOLDA(amoi, t, amoi)
+      HOLDA(ps, t, psur, K_PSUR)
+      if constexpr (!kDerive) HOLDA(pa, t, patm, K_PATM)
+      HOLDA(qa, t, qatm, K_QATM)
+      HOLDA(ta, t, tatm, K_TATM)
+      HOLDA(u, t, uatm, K_UATM)
+      HOLDA(v, t, vatm, K_VATM)
+      if constexpr (!(kDerive && VAR == 1)) HOLDA(amoi, t, amoi, K_AMOI)
       if constexpr (kDerive) {
         if (d_ef) {
           Vec<C, R> pa_l = {};
-          if (g.patm) pa_l = LD(g.patm, j0, nt);
+          if (g.patm || cbit(cm, K_PATM)) pa_l = LDU(g.patm, cbit(cm, K_PATM), j0, nt);
           h_pa = g.patm;
+          hold(K_PATM);
           FOR_C taef.v[i] = ta_exner(ta.v[i], ps.v[i], pa_l.v[i]);
         }
         if constexpr (VAR == 1) {
@@ -539,28 +596,31 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
             FOR_C w.v[i] = wind(u.v[i], v.v[i]);
             if (d_amv) {
               Vec<C, R> am = {};
-              if (g.amoi) am = LD(g.amoi, j0, nt);
+              if (g.amoi || cbit(cm, K_AMOI)) am = LDU(g.amoi, cbit(cm, K_AMOI), j0, nt);
               h_amoi = g.amoi;
+              hold(K_AMOI);
               FOR_C amv.v[i] = rate_num(am.v[i], w.v[i], ps.v[i]);
             }
             if (d_mvp) {
               Vec<C, R> am = {};
-              if (tp.uv[0].amom) am = LD(tp.uv[0].amom, j0, nt);
+              if (tp.uv[0].amom || cbit(cm, kUvBit0 + KU_AMOM))
+                am = LDU(tp.uv[0].amom, cbit(cm, kUvBit0 + KU_AMOM), j0, nt);
               h_amom = tp.uv[0].amom;
+              hold(kUvBit0 + KU_AMOM);
               FOR_C mvp.v[i] = mom_num(am.v[i], w.v[i], ps.v[i]);
             }
           }
         }
       }
       if constexpr (!kPrefetch) {
-        HOLD(cmoi, t, cmoi)
-        HOLD(chea, t, chea)
+        HOLD(cmoi, t, cmoi, K_CMOI)
+        HOLD(chea, t, chea, K_CHEA)
       }
       if (g.qsur_in) qs = LD(g.qsur_in, j0, nt);  // may be written by this pass: never held
       if (g.meva_in) me = LD(g.meva_in, j0, nt);
       if constexpr (MERGED) {
-        if constexpr (!(kDerive && VAR == 1)) HOLDA(amom, uv[0], amom)
-        if constexpr (!kPrefetch) HOLD(cmom, uv[0], cmom)
+        if constexpr (!(kDerive && VAR == 1)) HOLDA(amom, uv[0], amom, kUvBit0 + KU_AMOM)
+        if constexpr (!kPrefetch) HOLD(cmom, uv[0], cmom, kUvBit0 + KU_CMOM)
       }
       if constexpr (!(kDerive && VAR == 1)) {
         if (wind_new) FOR_C vel.v[i] = wind(u.v[i], v.v[i]);
@@ -702,8 +762,8 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       if ((stages & S_RSDR) && g.rsdr) ST(g.rsdr, j0, ns, rsdd);
     }
     if constexpr (!MERGED) {
-      if (j0 < P->n[1]) uv_grid<C, NT, R, TM>(tp, mt, 0, stages, j0, P->n[1], D_);
-      if (j0 < P->n[2]) uv_grid<C, NT, R, TM>(tp, mt, 1, stages, j0, P->n[2], D_);
+      if (j0 < P->n[1]) uv_grid<C, NT, R, TM, kUni>(tp, mt, 0, stages, j0, P->n[1], D_);
+      if (j0 < P->n[2]) uv_grid<C, NT, R, TM, kUni>(tp, mt, 1, stages, j0, P->n[2], D_);
     }
   }
 #undef HOLD
@@ -1616,9 +1676,18 @@ __global__ void atmos_finish_group_kernel(const FinishGroup g) {
   for (int64_t i = t; i < (int64_t)n_boundaries * a.stride; i += blockDim.x) a.shared[i] = 0.0;
 }
 
-__global__ void zero_kernel(double *x, int64_t n) {
+// One value in every cell j < n of an engine buffer, cell j at x[tiled(j, tpad)]: the mirror of
+// a constant field (fcx_bind_constant), written once at commit.  A lane stores the 16 B of its
+// C consecutive cells (C divides the layout tile, so they share one tile shift; engine buffers
+// are 256-B aligned); the cells of a partial last vector go out one by one, none past n.
+template <class R>
+__global__ __launch_bounds__(256) void fill_kernel(R *x, int64_t n, R value, int64_t tpad) {
+  constexpr int C = 16 / sizeof(R);
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += stride) x[j] = 0.0;
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u * C < n; u += stride) {
+    const int64_t j0 = u * C;
+    st<C, false, R>(x + (j0 >> kLayoutShift) * tpad, j0, n, splat<C, R>(value));
+  }
 }
 
 static int grid_for(int64_t units, int max_blocks = 256 * 8) {
@@ -2042,11 +2111,17 @@ int launch_atmos_fixup_group(const AtmosFused *afs, const int64_t *n_cells, int 
   return (int)hipGetLastError();
 }
 
-int launch_zero(double *x, int64_t n, void *stream) {
+int launch_fill(double *x, int64_t n, double value, bool f32, int64_t tpad, void *stream) {
   if (n <= 0) return 0;
-  hipLaunchKernelGGL(zero_kernel, dim3(grid_for(n)), dim3(256), 0,
-                     reinterpret_cast<hipStream_t>(stream), x, n);
+  if (!x || reinterpret_cast<uintptr_t>(x) % 16 || tpad < 0) return (int)hipErrorInvalidValue;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (f32)
+    hipLaunchKernelGGL(fill_kernel<float>, dim3(grid_for((n + 3) / 4)), dim3(256), 0, s, reinterpret_cast<float *>(x), n,
+                       (float)value, tpad);
+  else
+    hipLaunchKernelGGL(fill_kernel<double>, dim3(grid_for((n + 1) / 2)), dim3(256), 0, s, x, n, value, tpad);
   return (int)hipGetLastError();
 }
+
 
 }  // namespace fcx

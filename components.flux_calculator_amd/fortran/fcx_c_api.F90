@@ -78,6 +78,21 @@ MODULE fcx_c_api
       INTEGER(c_int64_t), VALUE :: n
       INTEGER(c_int) :: fcx_bind_field
     END FUNCTION
+    ! a namelist-constant input field (val_*_var_*): no array is read, uploaded or staged
+    FUNCTION fcx_bind_constant(engine, surface_type, grid, var, value) BIND(C, name='fcx_bind_constant')
+      IMPORT :: c_int, c_ptr, c_double
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int), VALUE :: surface_type, grid, var
+      REAL(c_double), VALUE :: value
+      INTEGER(c_int) :: fcx_bind_constant
+    END FUNCTION
+    FUNCTION fcx_constant_info(engine, surface_type, grid, var, kind) BIND(C, name='fcx_constant_info')
+      IMPORT :: c_int, c_int32_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int), VALUE :: surface_type, grid, var
+      INTEGER(c_int32_t), INTENT(OUT) :: kind
+      INTEGER(c_int) :: fcx_constant_info
+    END FUNCTION
     FUNCTION fcx_set_corrections(engine, enabled, init_date, corr, n, layout) BIND(C, name='fcx_set_corrections')
       IMPORT :: c_int, c_int32_t, c_int64_t, c_ptr
       TYPE(c_ptr), VALUE :: engine, corr

@@ -10,6 +10,8 @@
 ! plus the engine life cycle the host calls once (INTEGRATION.md):
 !   fcx_attach              after flux_calculator.F90:761 (all allocations/aliases final)
 !   fcx_register_average    for each type-0 output (optional: fused averaging)
+!   fcx_declare_constant    for each input the namelist gave a value (val_*_var_*) instead of
+!                           a sender (optional: the field is then never transferred)
 !   fcx_commit_engine       validate + device mirrors
 !   fcx_run_phase           fused coupling-step phase (replaces :902 and :972-991)
 !   fcx_start_phase /       the same phase in two halves: started (inputs taken, launch and
@@ -43,6 +45,7 @@ MODULE flux_calculator_calculate
     PUBLIC fcx_attach, fcx_register_average, fcx_commit_engine, fcx_run_phase, fcx_detach
     PUBLIC fcx_register_abort, fcx_start_phase, fcx_finish_phase, fcx_hand_over_field
     PUBLIC fcx_allocate_field, fcx_free_field
+    PUBLIC fcx_declare_constant
 
     TYPE(c_ptr), SAVE :: engine = c_null_ptr
     ! What fcx_attach bound.  The reference subroutines take the bottom model, the type count,
@@ -267,6 +270,33 @@ CONTAINS
                                          c_loc(w8(1))), 'fcx_set_regrid_matrix')
         DEALLOCATE(w8)
     END SUBROUTINE set_matrix
+
+    ! An input field the namelist gave a value instead of a sender (val_bottom_var_* /
+    ! val_atmos_var_* > -0.99e20, flux_calculator.F90:444-549: init_localvar fills it once, no
+    ! model ever sends it).  Called between fcx_attach and fcx_commit_engine, once per such
+    ! field, with the local_field fcx_attach bound: the array must hold `value` in every cell
+    ! (checked here, once; a host that changed it has no constant and the run stops), and from
+    ! then on the engine neither reads nor writes it -- no upload, no staging, no mapping.
+    ! Aliases (distribute_input_field, basic:334-358) follow: every slot bound to the same
+    ! address becomes the constant, so an atmosphere constant is declared once, for type 0.
+    SUBROUTINE fcx_declare_constant(surface_type, which_grid, my_idx, value, local_field)
+        INTEGER,                                  INTENT(IN) :: surface_type, which_grid, my_idx
+        REAL(kind=wp),                            INTENT(IN) :: value
+        TYPE(local_fields_type), DIMENSION(0:,:), INTENT(IN) :: local_field
+        CHARACTER(len=160) :: msg
+        IF (.NOT. c_associated(engine)) CALL contract_error('fcx_declare_constant', 'no flux engine attached')
+        IF (surface_type < 0 .OR. surface_type > MAX_SURFACE_TYPES .OR. which_grid < 1 .OR. which_grid > 3 .OR. &
+            my_idx < 1 .OR. my_idx > MAX_VARNAMES) CALL contract_error('fcx_declare_constant', 'slot out of range')
+        IF (.NOT. ASSOCIATED(local_field(surface_type, which_grid)%var(my_idx)%field)) &
+            CALL contract_error('fcx_declare_constant', 'the field is not associated')
+        IF (ANY(local_field(surface_type, which_grid)%var(my_idx)%field /= value)) THEN
+            WRITE (msg, '(A,I0,A,I0,A,I0,A,ES23.15)') 'local_field(', surface_type, ',', which_grid, ')%var(', my_idx, &
+                ') does not hold the declared constant in every cell: ', value
+            CALL contract_error('fcx_declare_constant', TRIM(msg))
+        ENDIF
+        CALL check(fcx_bind_constant(engine, INT(surface_type, c_int), INT(which_grid, c_int), INT(my_idx, c_int), &
+                                     REAL(value, c_double)), 'fcx_bind_constant')
+    END SUBROUTINE fcx_declare_constant
 
     ! output_field(j) with surface_type 0 (flux_calculator.F90:909-918, 999-1008)
     SUBROUTINE fcx_register_average(early, which_grid, my_idx)

@@ -100,6 +100,8 @@ SIGNATURES = [
     ("fcx_comm_verify", _I, [_P, _I]),
     ("fcx_set_abort_handler", _I, [_P]),
     ("fcx_abort", _I, [_c.c_char_p]),
+    ("fcx_bind_constant", _I, [_P, _I, _I, _I, _c.c_double]),
+    ("fcx_constant_info", _I, [_P, _I, _I, _I, _c.POINTER(_I32)]),
 ]
 
 

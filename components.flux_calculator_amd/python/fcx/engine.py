@@ -1,5 +1,6 @@
 """Engine: one libfcx engine bound to a LocalFields (one rank, one GPU)."""
 import ctypes
+import warnings
 
 import numpy as np
 
@@ -19,7 +20,7 @@ class Engine:
 
     def __init__(self, lf: LocalFields, num_surface_types, methods, corrections=None,
                  averages=(), regrid=None, device=0, stream=None, atmos=None, options=None, remaps=None,
-                 lib=None, commit=True):
+                 lib=None, commit=True, use_constants=True):
         """atmos: exchange -> atmosphere accumulation, dict with
              local   : fcx.parallel.LocalAtmos of this rank
              fields  : [(phase, surface_type, grid, name, out_array[n_atmos])]
@@ -32,7 +33,12 @@ class Engine:
                  "fields": [(phase, surface_type, grid, name, out_array[n_dst])]}
         options: {name: value} for fcx_set_option.
         lib: another libfcx build from _lib.load_path (A/B measurement tools only).
-        commit=False: bind only (no GPU touched); plan_check() then audits the plans on the host."""
+        commit=False: bind only (no GPU touched); plan_check() then audits the plans on the host.
+        use_constants: the fields lf.constant records (namelist val_* values) are declared with
+             fcx_bind_constant after their arrays are bound, so the engine never transfers them;
+             a recorded field whose array no longer holds the value in every cell (a host that
+             wrote it after set-up) stays an ordinary array, with a RuntimeWarning and an entry
+             in Engine.dropped_constants.  False: every field is an array."""
         self.lib = lib if lib is not None else _lib.load()
         self.lf = lf
         self.T = int(num_surface_types)
@@ -61,6 +67,21 @@ class Engine:
                     raise TypeError(f"slot {(s, g, var)}: {dtype_name(a)} array in a {dtype} LocalFields")
                 n = a.shape[0]
                 _lib.check(self.lib.fcx_bind_field(h, s, g, var, ctypes.c_void_p(data_ptr(a)), n, flags))
+            self.constants = {}  # (s, g, name) -> value of the slots declared constant
+            self.dropped_constants = {}  # recorded constants whose array no longer holds the value
+            if use_constants:
+                for (s, g, name), value in getattr(lf, "constant", {}).items():
+                    a = lf.field.get((s, g, name))
+                    if a is None or not bool((a == value).all()):
+                        # the Fortran drop-in stops here (fcx_declare_constant); a Python host may
+                        # have rewritten the field on purpose, so it is told and the array is used
+                        self.dropped_constants[(s, g, name)] = float(value)
+                        warnings.warn(f"{name}({s},{g}) is recorded as the constant {value} but its array "
+                                      "no longer holds it in every cell: bound as an ordinary array",
+                                      RuntimeWarning, stacklevel=2)
+                        continue
+                    _lib.check(self.lib.fcx_bind_constant(h, s, g, IDX[name], float(value)))
+                    self.constants[(s, g, name)] = float(value)
             if corrections is not None:
                 init_date, corr = corrections
                 corr = np.ascontiguousarray(corr, dtype=np.float64)
@@ -235,6 +256,18 @@ class Engine:
         p = ctypes.POINTER(ctypes.c_double)()
         _lib.check(self.lib.fcx_device_ptr(self.h, s, g, IDX[name], ctypes.byref(p)))
         return ctypes.cast(p, ctypes.c_void_p).value
+
+    def constant_info(self, s, g, name):
+        """fcx_constant_info: 0 the slot is an array, 1 a constant without a device array, 2 a
+        constant in a device array the engine filled at commit."""
+        k = ctypes.c_int32()
+        _lib.check(self.lib.fcx_constant_info(self.h, int(s), int(g), IDX[name], ctypes.byref(k)))
+        return k.value
+
+    def bind_constant(self, s, g, name, value):
+        """fcx_bind_constant on an uncommitted engine (commit=False)."""
+        _lib.check(self.lib.fcx_bind_constant(self.h, int(s), int(g), IDX[name], float(value)))
+        self.constants[(s, g, name)] = float(value)
 
     def device_layout(self):
         """(tile, tile_stride) of the engine-owned mirrors: cell j of a device buffer is at

@@ -37,6 +37,10 @@ class LocalFields:
         self.field = {}  # (s, g, name) -> array
         self.allocated = set()  # (s, g, name) with realarray%allocated = .TRUE.
         self.put_to = {}  # (s, g, name) -> bitmask t=1,u=2,v=4
+        # (s, g, name) -> value of a namelist-constant input (val_* > -0.99e20, init_localvar
+        # basic:313-330): the array holds it in every cell, and the engine binds it with
+        # fcx_bind_constant instead of the array
+        self.constant = {}
 
     # ---- helpers
     def _new(self, n, value=None):
@@ -70,11 +74,29 @@ class LocalFields:
         a = self._new(self.grid_size[g - 1], value)
         self.field[(s, g, name)] = a
         self.allocated.add((s, g, name))
+        self.constant.pop((s, g, name), None)
+        return a
+
+    def set_constant(self, name, s, g, value):
+        """init_localvar (basic:313-330) of a field no model sends: the array is filled, so the
+        CPU oracle and a host reading it see the value, and the slot is recorded as constant."""
+        value = float(value)
+        if not np.isfinite(value):
+            raise ValueError(f"constant {name}({s},{g}): {value} is not finite")
+        a = self.field[(s, g, name)]
+        if isinstance(a, np.ndarray):
+            a[:] = value
+        else:
+            a.fill_(value)
+        for key, b in self.field.items():  # every alias holds the same array
+            if b is a:
+                self.constant[key] = value
         return a
 
     def set_array(self, name, s, g, array, allocated=True):
         """Bind an existing array (e.g. synthetic data) to a slot."""
         self.field[(s, g, name)] = array
+        self.constant.pop((s, g, name), None)
         if allocated:
             self.allocated.add((s, g, name))
         else:
@@ -88,11 +110,20 @@ class LocalFields:
             if j == to_s or (j != from_s and to_s == 0):
                 self.field[(j, g, name)] = src
                 self.allocated.discard((j, g, name))
+                self._carry_constant((from_s, g, name), (j, g, name))
 
     def alias(self, name, s, g, from_s=1):
         """'copy' method (prepare:36-38) or uniform output alias (basic:205)."""
         self.field[(s, g, name)] = self.field[(from_s, g, name)]
         self.allocated.discard((s, g, name))
+        self._carry_constant((from_s, g, name), (s, g, name))
+
+    def _carry_constant(self, src, dst):
+        """dst => src: an alias of a constant is that constant, an alias of an array is not"""
+        if src in self.constant:
+            self.constant[dst] = self.constant[src]
+        else:
+            self.constant.pop(dst, None)
 
     def slots(self):
         for (s, g, name), a in self.field.items():
@@ -120,6 +151,7 @@ class LocalFields:
             new.field[key] = conv[id(a)]
         new.allocated = set(self.allocated)
         new.put_to = dict(self.put_to)
+        new.constant = dict(self.constant)
         return new
 
 

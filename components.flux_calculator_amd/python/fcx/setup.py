@@ -140,6 +140,7 @@ class FluxCalculatorSetup:
         lf = self.local_field
         lf.field[(s, g, var)] = lf._new(self.grid_size[g - 1], value)
         lf.allocated.add((s, g, var))
+        lf.constant.pop((s, g, var), None)
         if reset_put_to:
             lf.put_to.pop((s, g, var), None)
 
@@ -148,8 +149,10 @@ class FluxCalculatorSetup:
         lf = self.local_field
         if src in lf.field:
             lf.field[dst] = lf.field[src]
+            lf._carry_constant(src, dst)
         else:
             lf.field.pop(dst, None)
+            lf.constant.pop(dst, None)
 
     def distribute_input_field(self, var, g, from_s, to_s):
         """basic:334-358."""
@@ -181,7 +184,7 @@ class FluxCalculatorSetup:
                     self._allocate(i, gi, name)
                     v = vals[i - 1, j]
                     if v > -0.99e20:
-                        self.local_field.field[(i, gi, name)][:] = v  # init_localvar
+                        self.local_field.set_constant(name, i, gi, v)  # init_localvar
                     elif v < -1.99e20:
                         self.distribute_input_field(name, gi, 1, 0)
                     else:
@@ -195,7 +198,7 @@ class FluxCalculatorSetup:
                 self._allocate(0, gi, name)
                 v = vals[j]
                 if v > -0.99e20:
-                    self.local_field.field[(0, gi, name)][:] = v
+                    self.local_field.set_constant(name, 0, gi, v)
                 else:
                     self.add_input_field(name, "A", 0, gi)
                 self.distribute_input_field(name, gi, 0, 0)

@@ -110,6 +110,30 @@ int fcx_set_method(fcx_engine *e, int flux, int surface_type, int method);
  * several slots are aliases (basic:334-358, prepare:36-38) and share one device buffer. */
 int fcx_bind_field(fcx_engine *e, int surface_type, int grid, int var, double *ptr, int64_t n,
                    int flags);
+/* A namelist-constant input field (val_bottom_var_* / val_atmos_var_*, flux_calculator.F90:
+ * 444-549: filled once by init_localvar, never received, never written): the slot holds
+ * `value` in every cell.  Call before fcx_commit.  An unbound slot becomes bound, with no
+ * caller array at all; a slot bound to an array turns constant together with EVERY slot bound
+ * to the same address (the aliases of distribute_input_field, basic:334-358), and from then on
+ * the engine neither reads nor writes that array: it is not uploaded, staged, mapped or given
+ * a span.  Where only the flux pass reads the field, the fp64 generic and CCLM kernels without
+ * register averages take it as a wave-uniform value out of the parameter block: no device
+ * array, no vector load, and fcx_algorithmic_bytes does not count it.  Every other reader --
+ * the fp32, MOM5, RCO and register-average kernels (no registers to spare for it, or a slower
+ * step with it), a regridding, an average's FARE or field, the atmosphere
+ * accumulation, a remap, fcx_device_ptr -- reads a device array of the engine's own, filled
+ * once (in an fp32 engine with the value rounded to float once, as a bound float array holds
+ * it).  Either way a constant costs no host-link traffic and no place in the staging arena,
+ * and results are those of a bound array holding `value`, bit for bit.  fcx_upload_field of a
+ * constant slot is a no-op.  `value` must be finite (FCX_E_ARG).  A constant slot that some plan would write --
+ * a computed flux, a 'copy' target, a regrid destination, an average's type-0 output, RSDR --
+ * is a named FCX_E_STATE error of fcx_plan_check / fcx_commit. */
+int fcx_bind_constant(fcx_engine *e, int surface_type, int grid, int var, double value);
+/* after fcx_commit: *kind = 0 the slot is not a constant; 1 a constant no device array has
+ * been filled for (so far only launches that take it as a wave-uniform value read it); 2 a
+ * constant in a device array the engine filled itself, at commit for a reader outside the flux
+ * pass, later when the first launch that streams it is planned or fcx_device_ptr asks for it */
+int fcx_constant_info(const fcx_engine *e, int surface_type, int grid, int var, int32_t *kind);
 /* bias_corrections: lcorrections(E_MASS_EVAP_CORRECTION), init_date, corrections(1,:,:) */
 int fcx_set_corrections(fcx_engine *e, int enabled, int32_t init_date, const double *corr,
                         int64_t n, int layout);
