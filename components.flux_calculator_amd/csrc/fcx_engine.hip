@@ -556,11 +556,15 @@ extern "C" int fcx_bind_field(fcx_engine *e, int s, int g, int var, double *ptr,
                 kVarNames[var0(var)], s, g == 1 ? "t" : g == 2 ? "u" : "v", (long long)n,
                 (long long)e->n[g - 1]);
   const bool on_dev = flags & FCX_MEM_DEVICE;
+  // A buffer is as long as the largest grid its pointer is bound on, not as the array the
+  // caller declared: cells past the slot's grid size are never read or written, by a kernel or
+  // by a transfer (an output is never uploaded, so a download of its declared length would
+  // write whatever its mirror held over the caller's cells [grid_size, n)).
   auto it = e->by_ptr.find(ptr);
   int b;
   if (it == e->by_ptr.end()) {
     Buffer bf;
-    bf.n = n;
+    bf.n = e->n[g - 1];
     if (on_dev) {
       bf.dev = ptr;
       bf.external = true;
@@ -575,7 +579,7 @@ extern "C" int fcx_bind_field(fcx_engine *e, int s, int g, int var, double *ptr,
     b = it->second;
     if (e->bufs[b].external != on_dev)
       return fail(FCX_E_ARG, "pointer bound both as host and as device memory");
-    e->bufs[b].n = std::max(e->bufs[b].n, n);
+    e->bufs[b].n = std::max(e->bufs[b].n, e->n[g - 1]);
   }
   e->slot[s][g - 1][var0(var)] = b;
   e->allocated[s][g - 1][var0(var)] = (flags & FCX_ALLOCATED) != 0;

@@ -107,7 +107,11 @@ int fcx_set_stream(fcx_engine *e, void *hip_stream);
 /* methods(my_bottom_model, surface_type) of one which_* table */
 int fcx_set_method(fcx_engine *e, int flux, int surface_type, int method);
 /* local_field(surface_type, grid)%var(var)%field => ptr(1:n).  Identical pointers in
- * several slots are aliases (basic:334-358, prepare:36-38) and share one device buffer. */
+ * several slots are aliases (basic:334-358, prepare:36-38) and share one device buffer.
+ * n >= grid_size(grid) (FCX_E_ARG otherwise).  An array may be longer than its grid: cells
+ * past the slot's grid size -- for a pointer bound on several grids, past the largest of them
+ * -- are never read and never written, by a kernel or by a transfer, whatever the memory
+ * (device arrays in place, caller heap arrays, fcx_host_malloc arrays as spans or in place). */
 int fcx_bind_field(fcx_engine *e, int surface_type, int grid, int var, double *ptr, int64_t n,
                    int flags);
 /* A namelist-constant input field (val_bottom_var_* / val_atmos_var_*, flux_calculator.F90:
