@@ -55,6 +55,45 @@ int fail(int code, const char *fmt, ...) {
     if (e_ != hipSuccess) return fail(FCX_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
   } while (0)
 
+// A device allocation and its owner: move-only, freed with the owner.  A null pointer makes
+// no HIP call, so an engine that never reached the device is destroyed without one.
+template <class T>
+struct DevArray {
+  T *p = nullptr;
+  size_t bytes = 0;
+  DevArray() = default;
+  DevArray(const DevArray &) = delete;
+  DevArray &operator=(const DevArray &) = delete;
+  DevArray(DevArray &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr, o.bytes = 0; }
+  DevArray &operator=(DevArray &&o) noexcept {
+    if (this != &o) {
+      reset();
+      p = o.p, bytes = o.bytes;
+      o.p = nullptr, o.bytes = 0;
+    }
+    return *this;
+  }
+  ~DevArray() { reset(); }
+  void reset() {
+    if (p) (void)hipFree(p);
+    p = nullptr, bytes = 0;
+  }
+  hipError_t alloc(size_t nbytes) {
+    reset();
+    const hipError_t r = hipMalloc((void **)&p, nbytes);
+    if (r == hipSuccess) bytes = nbytes; else p = nullptr;
+    return r;
+  }
+  // v's elements on the device; an empty v gets one element's allocation and no copy
+  template <class U>
+  int upload(const std::vector<U> &v) {
+    HIP_TRY(alloc(std::max<size_t>(v.size(), 1) * sizeof(U)));
+    if (!v.empty()) HIP_TRY(hipMemcpy(p, v.data(), v.size() * sizeof(U), hipMemcpyHostToDevice));
+    return FCX_OK;
+  }
+  operator T *() const { return p; }
+};
+
 const char *kVarNames[kNumVars] = {
     "ALBE", "ALBA", "AMOI", "AMOM", "FARE", "FICE", "PATM", "PSUR", "QATM", "TATM", "TSUR", "UATM",
     "VATM", "U10M", "V10M", "CMOM", "CMOI", "CHEA", "QSUR", "HLAT", "HSEN", "MEVA", "MPRE", "MRAI",
@@ -69,14 +108,28 @@ struct StageRef {
   size_t soff = 0;
 };
 
-struct Buffer {
+// One caller array and its device mirror: a bound field, an atmosphere output or a remap
+// output.  Every transport works on this type (for_each_mirror).
+struct HostMirror {
   double *host = nullptr;  // caller array (nullptr for device-bound)
   double *dev = nullptr;   // device memory (engine pool or caller's)
+  // elements, settled at fcx_commit: the bound length of a field, n_atmos of an atmosphere
+  // output, n_dst of a remap output
   int64_t n = 0;
   bool external = false;   // caller-owned device memory (or a host array used in place)
-  bool in_place = false;   // a host array the kernels use through its mapped address
   StageRef st;
+  // some transport moves it between host and device (not device-bound, not used in place)
+  bool moves_over_link() const { return !external || st.sp >= 0; }
+};
+
+// bytes of a mirror of n elements of es bytes: an empty array still has one element's worth,
+// so that it has an address of its own in a pool and a block lookup has a byte to find
+inline size_t mirror_bytes(int64_t n, size_t es) { return (size_t)std::max<int64_t>(n, 1) * es; }
+
+struct Buffer : HostMirror {
+  bool in_place = false;   // a host array the kernels use through its mapped address
   int span = -1;           // fcx_host_malloc array moved by the span transport: its Span
+  bool moves_over_link() const { return HostMirror::moves_over_link() || span >= 0; }
   // fcx_bind_constant: a namelist-constant input.  No caller array (host stays nullptr and the
   // buffer is never external), so no transport ever sees it; its mirror in the engine's pools
   // is filled with cval once at fcx_commit and only ever read.
@@ -89,12 +142,19 @@ struct Buffer {
   bool filled = false;
 };
 
+// A field of (s, g, var) summed to another grid in `phase`: an atmosphere output (the
+// exchange -> atmosphere accumulation) or an output of a remap.
+struct OutField {
+  int phase, s, g, var;
+  HostMirror m;
+};
+
 // The span transport (FCX_OPT_LIB_SPANS) of fcx_host_malloc arrays: one device buffer per
 // host slab the engine's arrays sit in, laid out like the host memory from `lo` on, so that
 // arrays adjacent in host memory are adjacent on the device and move as ONE copy.
 struct Span {
   uintptr_t lo = 0;  // host address of the device buffer's first byte
-  char *dev = nullptr;
+  DevArray<char> dev;
   size_t bytes = 0;
 };
 
@@ -120,18 +180,49 @@ struct Xfer {
   int64_t n;
 };
 
+// A sparse map in CSR by destination, every row's links in the order they were given, on the
+// host and on the device: the four regrid matrices, the atmosphere map and every remap.
 struct Csr {
   bool set = false;
   int64_t n_dst = 0;
-  std::vector<int32_t> row_ptr, col;
+  std::vector<int32_t> row, col;
   std::vector<double> w;
-  int32_t *d_row = nullptr, *d_col = nullptr;
-  double *d_w = nullptr;
+  DevArray<int32_t> d_row, d_col;
+  DevArray<double> d_w;  // (floats for the regrid matrices of an fp32 engine)
+
+  // The stable coordinate -> CSR fill: link k goes from cell src[k] (src == nullptr: from
+  // cell k) to row dst[k], both counted from `base` (regrid links from 1, atmosphere and
+  // remap links from 0).  The caller has checked the links' range.
+  void build(int64_t n, int64_t links, const int32_t *src, const int32_t *dst, const double *wk, int base) {
+    set = true;
+    n_dst = n;
+    row.assign((size_t)n + 1, 0);
+    for (int64_t k = 0; k < links; ++k) row[(size_t)(dst[k] - base) + 1]++;
+    for (int64_t d = 0; d < n; ++d) row[(size_t)d + 1] += row[(size_t)d];
+    col.assign((size_t)links, 0);
+    w.assign((size_t)links, 0.0);
+    std::vector<int32_t> fill(row.begin(), row.end() - 1);
+    for (int64_t k = 0; k < links; ++k) {
+      const int32_t at = fill[(size_t)(dst[k] - base)]++;
+      col[(size_t)at] = src ? src[k] - base : (int32_t)k;
+      w[(size_t)at] = wk[k];
+    }
+  }
+
+  // with_col false: a map whose row d holds cells row[d] .. row[d + 1] - 1 themselves
+  int upload(bool f32_weights, bool with_col = true) {
+    if (int r = d_row.upload(row)) return r;
+    if (with_col)
+      if (int r = d_col.upload(col)) return r;
+    if (!f32_weights) return d_w.upload(w);
+    return d_w.upload(std::vector<float>(w.begin(), w.end()));  // rounded once
+  }
 };
 
 struct Plan {
   Params host{};
-  Params *dev = nullptr;
+  DevArray<Params> dev;
+  DevArray<double> rec;  // owner of host.rec
   std::vector<int> reads, writes;  // buffer ids
   std::vector<int> const_reads;    // constant buffers the launch streams (never transferred)
   int variant = 0;                 // T=1 specialisation (LaunchConfig::variant)
@@ -214,11 +305,11 @@ struct fcx_engine {
   bool lcorr = false;
   int32_t init_date = 0;
   std::vector<double> corr_mm;  // [12][n_t]
-  void *corr_dev = nullptr;  // [12][n_t] in the engine precision
+  DevArray<void> corr_dev;  // [12][n_t] in the engine precision
   Csr rg[4];
   std::vector<std::pair<int, std::pair<int, int>>> averages;  // (phase, (grid, var))
   std::map<std::pair<uint32_t, int>, Plan> plans;               // (stages, avg phase mask)
-  void *pool = nullptr;
+  DevArray<void> pool;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool timed = false;
   bool gpu_ready = false;
@@ -226,42 +317,36 @@ struct fcx_engine {
   LaunchConfig launch;      // fcx_set_option
   bool specialize = true;
   // exchange -> atmosphere accumulation
-  struct AtmosField {
-    int phase, s, g, var;
-    double *out_host = nullptr, *out_dev = nullptr;
-    bool external = false;
-    StageRef st;
-  };
   int64_t n_atmos = -1;
-  std::vector<int32_t> atm_row, atm_col;
-  std::vector<double> atm_w;
+  // by atmosphere cell; contiguous (the exchange cells ordered by atmosphere cell): row d
+  // holds the cells row[d] .. row[d + 1] - 1 themselves, and there is no column array
+  Csr atm;
   bool atm_contiguous = true;
-  int32_t *d_atm_row = nullptr, *d_atm_col = nullptr, *d_atm_idx = nullptr;
+  DevArray<int32_t> d_atm_idx;
   // the fused path's maps (which launch reads which: compact_map): a 4-B index per cell
   // (d_atm_idx) and the compacted map (AtmosFused::seg_*: [words] start bits, [words + 1]
   // prefix counts, [segments] atmosphere cells, one allocation)
-  void *d_atm_seg = nullptr;
-  int32_t *d_atm_tile_a0 = nullptr;  // the compacted map's first cell of every wave tile
+  DevArray<void> d_atm_seg;
+  DevArray<int32_t> d_atm_tile_a0;  // the compacted map's first cell of every wave tile
   int64_t atm_seg_words = 0, atm_segments = 0;
   std::vector<int32_t> atm_idx;
   // atmosphere cells without exchange cells (land, on a real intersection grid): the fused
   // accumulation has no segment for them, so their zero sums are stored after its launch
   std::vector<int32_t> atm_empty;
-  int32_t *d_atm_empty = nullptr;
+  DevArray<int32_t> d_atm_empty;
   int32_t atm_maxseg = 0;
-  double *d_atm_xrec = nullptr;    // [tiles][kXRec] crossing records (fix-up kernel)
+  DevArray<double> d_atm_xrec;     // [tiles][kXRec] crossing records (fix-up kernel)
   int64_t atm_crossings = 0;       // 128-cell tile boundaries inside a segment of the map
   bool atm_halo = true;            // FCX_OPT_ATMOS_HALO: halo tiles where they apply
-  double *d_atm_w = nullptr;
-  std::vector<AtmosField> atm_fields;
+  std::vector<OutField> atm_fields;
   double *atm_shared = nullptr;
   int32_t atm_nb = 0, atm_stride = 0, atm_left = -1, atm_right = -1;
   bool own_shared = false;        // fcx_set_atmos_boundaries: the engine allocates the slots
-  double *atm_shared_own = nullptr;
+  DevArray<double> atm_shared_own;
   struct fcx_comm *comm = nullptr;  // fcx_set_comm: the engine completes its boundary slots
   bool atm_done = false;            // the accumulation of the current run has been launched
   bool exchanged = false;           // ... and its boundary slots completed (comm attached)
-  void *atm_pool = nullptr;
+  DevArray<void> atm_pool;
   int64_t atm_out_tpad = 0;  // tile-blocked atmosphere outputs (kernels: tiled(a, atm_out_tpad))
   // Per-cell atmosphere records (FCX_OPT_ATM_RECORDS): atm_pool holds one record of every
   // registered field per atmosphere cell, [a][field], which the kernels write (field k at
@@ -270,7 +355,7 @@ struct fcx_engine {
   // filled from the records by atm_unpack before every one.
   int atm_records_opt = 2;   // 0 never, 1 wherever the layout applies, 2 auto
   bool atm_records = false;  // the layout is in use (decided at fcx_commit)
-  void *atm_soa = nullptr;
+  DevArray<void> atm_soa;
   size_t atm_soa_bytes = 0;
   int atm_soa_sp = -1;       // its staging pool (StagePool::dev set when atm_soa is allocated)
   bool atmos_in_run = true;
@@ -279,21 +364,12 @@ struct fcx_engine {
   std::unique_ptr<FieldUploader> uploader;  // fcx_upload_field
   std::vector<char> field_sent;             // buffers fcx_upload_field staged for the coming run
   // exchange -> model remaps (SCRIP links, CSR by destination in link order)
-  struct RemapField {
-    int phase, s, g, var;
-    double *out_host = nullptr, *out_dev = nullptr;
-    bool external = false;
-    StageRef st;
-  };
   struct Remap {
     int64_t n_dst = 0, n_links = 0;
     int32_t max_src = -1;
-    std::vector<int32_t> row, col;
-    std::vector<double> w;
-    int32_t *d_row = nullptr, *d_col = nullptr;
-    double *d_w = nullptr;
-    std::vector<RemapField> fields;
-    void *pool = nullptr;
+    Csr map;
+    std::vector<OutField> fields;
+    DevArray<void> pool;
     size_t pool_bytes = 0;
     // gather scatter of the map: distinct 64-B segments of a field array (8 fp64 cells) the
     // links of a 256-destination block touch, per link (sampled at commit).  About 0.3 on
@@ -302,7 +378,7 @@ struct fcx_engine {
   };
   std::vector<Remap> remaps;
   int remap_pack = 2;        // FCX_OPT_REMAP_PACK: 0 never, 1 always, 2 launches of >= 2 fields
-  void *d_rec = nullptr;     // remap records scratch (pack_records), shared by every remap launch
+  DevArray<void> d_rec;      // remap records scratch (pack_records), shared by every remap launch
   size_t rec_bytes = 0;
   const Plan *rec_plan = nullptr;  // the whole-phase plan the current run launched (its records)
   bool rec_written = false;        // the last flux launch wrote its plan's remap records
@@ -338,7 +414,7 @@ struct fcx_engine {
   // 0 when the field buffers are plain contiguous arrays
   bool tiled_opt = true;
   int64_t tpad = 0;
-  std::vector<void *> tiled_pools;  // the pools of a tiled engine (alloc_tiled)
+  std::vector<DevArray<void>> tiled_pools;  // the pools of a tiled engine (alloc_tiled)
   // fcx_plan_check: plans built on the host only (no device memory; bound buffers without a
   // mirror yet stand in with a non-null tag address), audited, and dropped
   bool plan_dry = false;
@@ -362,6 +438,25 @@ struct fcx_engine {
 };
 
 static void stage_free(fcx_engine *e);
+
+// The one walk over an engine's host-bound arrays.  fn(OutField &, kind, k): every atmosphere
+// output (k: its index, which is its column of the records and its slot of the tiled pool),
+// then every remap's outputs (k: the remap).
+enum class MirrorOf { Field, Atmos, Remap };
+
+template <class Fn>
+static void for_each_output(fcx_engine *e, Fn &&fn) {
+  for (size_t k = 0; k < e->atm_fields.size(); ++k) fn(e->atm_fields[k], MirrorOf::Atmos, k);
+  for (size_t r = 0; r < e->remaps.size(); ++r)
+    for (auto &f : e->remaps[r].fields) fn(f, MirrorOf::Remap, r);
+}
+
+// fn(HostMirror &, kind, k): every bound field (k: its buffer id), then every output
+template <class Fn>
+static void for_each_mirror(fcx_engine *e, Fn &&fn) {
+  for (size_t b = 0; b < e->bufs.size(); ++b) fn(static_cast<HostMirror &>(e->bufs[b]), MirrorOf::Field, b);
+  for_each_output(e, [&](OutField &f, MirrorOf kind, size_t k) { fn(f.m, kind, k); });
+}
 
 // ------------------------------------------------------------------ utilities
 
@@ -459,47 +554,18 @@ extern "C" int fcx_destroy(fcx_engine *e) {
   }
   (void)hipSetDevice(e->device);
   if (e->stream) (void)hipStreamSynchronize(e->stream);
-  for (auto &kv : e->plans) {
-    (void)hipFree(kv.second.dev);
-    (void)hipFree(kv.second.host.rec);
-  }
-  for (auto &r : e->rg) {
-    (void)hipFree(r.d_row);
-    (void)hipFree(r.d_col);
-    (void)hipFree(r.d_w);
-  }
-  (void)hipFree(e->corr_dev);
-  (void)hipFree(e->d_atm_row);
-  (void)hipFree(e->d_atm_seg);
-  (void)hipFree(e->d_atm_tile_a0);
-  (void)hipFree(e->d_atm_idx);
-  (void)hipFree(e->d_atm_empty);
-  (void)hipFree(e->d_atm_xrec);
-  (void)hipFree(e->d_atm_col);
-  (void)hipFree(e->d_atm_w);
-  (void)hipFree(e->atm_pool);
-  (void)hipFree(e->atm_soa);
-  (void)hipFree(e->atm_shared_own);
-  for (auto &r : e->remaps) {
-    (void)hipFree(r.d_row);
-    (void)hipFree(r.d_col);
-    (void)hipFree(r.d_w);
-    (void)hipFree(r.pool);
-  }
-  (void)hipFree(e->d_rec);
-  (void)hipFree(e->pool);
-  for (void *p : e->tiled_pools) (void)hipFree(p);
-  for (auto &sp : e->spans) (void)hipFree(sp.dev);
-  if (e->ev0) (void)hipEventDestroy(e->ev0);
-  if (e->ev1) (void)hipEventDestroy(e->ev1);
-  for (hipEvent_t ev : e->ev_in) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : e->ev_comp) (void)hipEventDestroy(ev);
-  for (hipEvent_t ev : e->ev_out) (void)hipEventDestroy(ev);
-  stage_free(e);
-  if (e->s_in) (void)hipStreamDestroy(e->s_in);
-  if (e->s_out) (void)hipStreamDestroy(e->s_out);
-  if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
+  // the device memory goes with the engine, every array through its owner (DevArray); the
+  // events and streams, which outlive it, are taken out first
+  std::vector<hipEvent_t> events{e->ev0, e->ev1, e->ev_stage_in};
+  for (const auto *evs : {&e->ev_in, &e->ev_comp, &e->ev_out}) events.insert(events.end(), evs->begin(), evs->end());
+  const hipStream_t streams[] = {e->s_in, e->s_out, e->own_stream ? e->stream : nullptr};
+  e->ev_stage_in = nullptr;
+  stage_free(e);  // (the arena's page-locked host images)
   delete e;
+  for (hipEvent_t ev : events)
+    if (ev) (void)hipEventDestroy(ev);
+  for (hipStream_t s : streams)
+    if (s) (void)hipStreamDestroy(s);
   return FCX_OK;
 }
 
@@ -654,25 +720,11 @@ extern "C" int fcx_set_regrid_matrix(fcx_engine *e, int which, int64_t nnz, cons
   if (which < 0 || which > 3) return fail(FCX_E_ARG, "regrid matrix %d unknown", which);
   static const int from_g[4] = {2, 3, 1, 1}, to_g[4] = {1, 1, 2, 3};
   const int64_t n_src = e->n[from_g[which] - 1], n_dst = e->n[to_g[which] - 1];
-  Csr &c = e->rg[which];
-  c.set = true;
-  c.n_dst = n_dst;
-  c.row_ptr.assign((size_t)n_dst + 1, 0);
-  for (int64_t k = 0; k < nnz; ++k) {
+  for (int64_t k = 0; k < nnz; ++k)
     if (src[k] < 1 || src[k] > n_src || dst[k] < 1 || dst[k] > n_dst)
       return fail(FCX_E_ARG, "regrid link %lld (%d -> %d) outside the local grids (io:183-191)",
                   (long long)k + 1, src[k], dst[k]);
-    c.row_ptr[(size_t)dst[k]]++;
-  }
-  for (int64_t d = 0; d < n_dst; ++d) c.row_ptr[(size_t)d + 1] += c.row_ptr[(size_t)d];
-  c.col.assign((size_t)nnz, 0);
-  c.w.assign((size_t)nnz, 0.0);
-  std::vector<int32_t> fill(c.row_ptr.begin(), c.row_ptr.end() - 1);
-  for (int64_t k = 0; k < nnz; ++k) {  // stable: link order kept inside each row
-    const int32_t at = fill[(size_t)dst[k] - 1]++;
-    c.col[(size_t)at] = src[k] - 1;
-    c.w[(size_t)at] = w[k];
-  }
+  e->rg[which].build(n_dst, nnz, src, dst, w, 1);
   return FCX_OK;
 }
 
@@ -835,7 +887,7 @@ static void plan_fused_atmos(fcx_engine *e, Plan &pl, uint32_t stages, int phase
       for (int slot = 0; slot < kFusedFields; ++slot)
         if (f.s == 0 && pl.host.ravg.out[slot] && b >= 0 && e->bufs[b].dev == pl.host.ravg.out[slot]) k = slot;
       if (k < 0 || af.out[k]) return;
-      af.out[k] = f.out_dev;
+      af.out[k] = f.m.dev;
       af.x[k] = e->bufs[b].dev;
       af.scol[k] = (int32_t)fi;
       ++nf;
@@ -852,20 +904,20 @@ static void plan_fused_atmos(fcx_engine *e, Plan &pl, uint32_t stages, int phase
     if (f.s == 1 && f.var == FCX_UMOM && (stages & S_UMOM) && b == e->buf(1, 2, FCX_UMOM)) k = 4;
     if (f.s == 1 && f.var == FCX_VMOM && (stages & S_VMOM) && b == e->buf(1, 3, FCX_VMOM)) k = 5;
     if (k < 0 || af.out[k]) return;  // not in registers (or twice): separate kernel
-    af.out[k] = f.out_dev;
+    af.out[k] = f.m.dev;
     af.x[k] = e->bufs[b].dev;
     af.scol[k] = (int32_t)fi;
     ++nf;
   }
   if (nf == 0) return;
   if (e->d_atm_seg) {
-    af.seg_bits = reinterpret_cast<const uint32_t *>(e->d_atm_seg);
+    af.seg_bits = reinterpret_cast<const uint32_t *>(e->d_atm_seg.p);
     af.seg_pre = reinterpret_cast<const int32_t *>(af.seg_bits + e->atm_seg_words);
     af.seg_atm = af.seg_pre + e->atm_seg_words + 1;
   }
   af.tile_a0 = e->d_atm_tile_a0;
   af.idx = e->d_atm_idx;
-  af.w = e->d_atm_w;
+  af.w = e->atm.d_w;
   af.xrec = e->d_atm_xrec;
   af.xrec_on = e->atm_crossings > 0;
 #ifdef FCX_AB_BUILD
@@ -907,7 +959,7 @@ static int plan_fused_records(fcx_engine *e, Plan &pl, uint32_t stages, int phas
       e->remap_pack == 0 || e->launch.cells_per_thread != 2 || !e->aligned16 || !P.merged_uv || P.n_max <= 0)
     return FCX_OK;
   const TypeParams &tp = P.type[0];
-  auto slot_of = [&](const fcx_engine::RemapField &f) -> int {
+  auto slot_of = [&](const OutField &f) -> int {
     const int b = e->buf(f.s, f.g, f.var);
     if (f.s != 1 || b < 0) return -1;
     if (f.var == FCX_MEVA && (stages & S_MEVA) && b == e->buf(1, 1, FCX_MEVA) && is_compute(tp.m_meva)) return 0;
@@ -927,7 +979,7 @@ static int plan_fused_records(fcx_engine *e, Plan &pl, uint32_t stages, int phas
   };
   for (size_t ri = 0; ri < e->remaps.size(); ++ri) {
     const auto &rm = e->remaps[ri];
-    std::vector<const fcx_engine::RemapField *> grp;
+    std::vector<const OutField *> grp;
     int gi = 0;
     auto try_group = [&]() -> bool {
       const int nf = (int)grp.size();
@@ -939,7 +991,8 @@ static int plan_fused_records(fcx_engine *e, Plan &pl, uint32_t stages, int phas
         pos[k] = (int8_t)i;
       }
       const int p = rec_width(e, nf);
-      HIP_TRY(hipMalloc(&P.rec, (size_t)P.n_max * p * sizeof(double)));
+      HIP_TRY(pl.rec.alloc((size_t)P.n_max * p * sizeof(double)));
+      P.rec = pl.rec;
       P.rec_p = p;
       for (int k = 0; k < 6; ++k) P.rec_pos[k] = pos[k];
       pl.rec_remap = (int)ri;
@@ -1430,7 +1483,7 @@ static int build_plan(fcx_engine *e, uint32_t stages, int avg_phases, Plan &pl) 
     if (int r = fill_constant(e, e->bufs[(size_t)b])) return r;
   plan_fused_atmos(e, pl, stages, avg_phases);
   if (int r = plan_fused_records(e, pl, stages, avg_phases)) return r;
-  HIP_TRY(hipMalloc(&pl.dev, sizeof(Params)));
+  HIP_TRY(pl.dev.alloc(sizeof(Params)));
   HIP_TRY(hipMemcpy(pl.dev, &P, sizeof(Params), hipMemcpyHostToDevice));
   return FCX_OK;
 }
@@ -1461,9 +1514,7 @@ static void decide_uniform(fcx_engine *e) {
         for (auto &a : e->averages) avg = avg || a.second.second == v;
         if (!in || avg || e->put_to[s][g - 1][v - 1]) array(s, g, v);
       }
-  for (auto &f : e->atm_fields) array(f.s, f.g, f.var);
-  for (auto &rm : e->remaps)
-    for (auto &f : rm.fields) array(f.s, f.g, f.var);
+  for_each_output(e, [&](OutField &f, MirrorOf, size_t) { array(f.s, f.g, f.var); });
 }
 
 // A constant field is an input: the slots a method or a regridding writes without any plan
@@ -1542,7 +1593,7 @@ static int get_plan(fcx_engine *e, uint32_t stages, int avg_phases, Plan **pl) {
   if (it == e->plans.end()) {
     Plan p;
     if (int r = build_plan(e, stages, avg_phases, p)) return r;
-    it = e->plans.emplace(key, p).first;
+    it = e->plans.emplace(key, std::move(p)).first;
   }
   *pl = &it->second;
   return FCX_OK;
@@ -1691,39 +1742,26 @@ extern "C" int fcx_host_free(void *ptr) {
 // kernel access through such a mapping missed the page it addressed.
 // Every other array keeps a mirror.  Returns the number of arrays used in place.
 static int map_host_arrays(fcx_engine *e) {
-  auto mapped = [&](void *host, size_t bytes) -> void * { return lib_block_device_ptr(host, bytes); };
   int count = 0;
-  for (auto &bf : e->bufs) {
-    if (bf.external || !bf.host) continue;
-    if (void *d = mapped(bf.host, (size_t)bf.n * e->esize)) {
-      bf.dev = reinterpret_cast<double *>(d);
-      bf.external = true;  // the engine neither owns nor copies it
-      bf.in_place = true;
-      e->zc_bytes += bf.n * (int64_t)e->esize;
-      ++count;
-      if (reinterpret_cast<uintptr_t>(d) % 16) e->aligned16 = false;
-    }
-  }
-  for (auto &f : e->atm_fields) {
-    if (f.external || !f.out_host) continue;
-    if (void *d = mapped(f.out_host, (size_t)std::max<int64_t>(e->n_atmos, 1) * e->esize)) {
-      f.out_dev = reinterpret_cast<double *>(d);
-      f.external = true;
-      e->zc_bytes += std::max<int64_t>(e->n_atmos, 0) * (int64_t)e->esize;
-      ++count;
-    }
-  }
-  for (auto &rm : e->remaps)
-    for (auto &f : rm.fields) {
-      if (f.external || !f.out_host) continue;
-      if (void *d = mapped(f.out_host, (size_t)std::max<int64_t>(rm.n_dst, 1) * e->esize)) {
-        f.out_dev = reinterpret_cast<double *>(d);
-        f.external = true;
-        e->zc_bytes += rm.n_dst * (int64_t)e->esize;
-        ++count;
-      }
-    }
+  for_each_mirror(e, [&](HostMirror &m, MirrorOf kind, size_t k) {
+    if (m.external || !m.host) return;
+    void *d = lib_block_device_ptr(m.host, mirror_bytes(m.n, e->esize));
+    if (!d) return;
+    m.dev = reinterpret_cast<double *>(d);
+    m.external = true;  // the engine neither owns nor copies it
+    e->zc_bytes += m.n * (int64_t)e->esize;
+    ++count;
+    if (kind != MirrorOf::Field) return;
+    e->bufs[k].in_place = true;
+    if (reinterpret_cast<uintptr_t>(d) % 16) e->aligned16 = false;
+  });
   return count;
+}
+
+// a caller heap array with a mirror of the engine's: not device or in-place memory, and not
+// fcx_host_malloc memory (which is copied by direct DMA)
+static bool on_heap(const fcx_engine *e, const HostMirror &m) {
+  return !m.external && m.host && !lib_block_device_ptr(m.host, mirror_bytes(m.n, e->esize));
 }
 
 // The span transport: every fcx_host_malloc array not used in place gets its mirror in the
@@ -1749,15 +1787,16 @@ static int map_lib_spans(fcx_engine *e, int *count) {
     Span sp;
     sp.lo = lo;
     sp.bytes = hi - lo;
-    hipError_t err = hipMalloc((void **)&sp.dev, sp.bytes);
+    hipError_t err = sp.dev.alloc(sp.bytes);
     if (err != hipSuccess)
       return fail(FCX_E_NOMEM, "hipMalloc(%zu) for a span of fcx_host_malloc arrays: %s", sp.bytes,
                   hipGetErrorString(err));
     const int id = (int)e->spans.size();
-    e->spans.push_back(sp);
+    char *const dev = sp.dev;
+    e->spans.push_back(std::move(sp));
     for (int b : kv.second) {
       Buffer &bf = e->bufs[(size_t)b];
-      bf.dev = reinterpret_cast<double *>(sp.dev + (reinterpret_cast<uintptr_t>(bf.host) - lo));
+      bf.dev = reinterpret_cast<double *>(dev + (reinterpret_cast<uintptr_t>(bf.host) - lo));
       bf.external = true;  // not in the engine's pools (the tiled layout is off for it)
       bf.span = id;
       if (reinterpret_cast<uintptr_t>(bf.dev) % 16) e->aligned16 = false;
@@ -1833,7 +1872,7 @@ static int span_copy(fcx_engine *e, std::vector<int> ids, bool h2d, hipStream_t 
     ++nr;
     if (s) {
       const Span &p = e->spans[(size_t)sp];
-      char *d = p.dev + (r0 - p.lo);
+      char *d = p.dev.p + (r0 - p.lo);
       char *h = reinterpret_cast<char *>(r0);
       HIP_TRY(h2d ? hipMemcpyAsync(d, h, r1 - r0, hipMemcpyDefault, s) : hipMemcpyAsync(h, d, r1 - r0, hipMemcpyDefault, s));
     }
@@ -1915,14 +1954,14 @@ static int alloc_tiled(fcx_engine *e) {
     }
   }
   for (int k = 0; k < npools; ++k) {
-    void *p = nullptr;
-    hipError_t err = hipMalloc(&p, bytes);
+    DevArray<void> p;
+    hipError_t err = p.alloc(bytes);
     if (err != hipSuccess)
       return fail(FCX_E_NOMEM, "hipMalloc(%zu) for the tiled field mirrors: %s", bytes, hipGetErrorString(err));
-    e->tiled_pools.push_back(p);
+    e->tiled_pools.push_back(std::move(p));
   }
   for (size_t b = 0; b < e->bufs.size(); ++b)
-    e->bufs[b].dev = reinterpret_cast<double *>((char *)e->tiled_pools[at[b].first] +
+    e->bufs[b].dev = reinterpret_cast<double *>((char *)e->tiled_pools[at[b].first].p +
                                                 (size_t)at[b].second * kLayoutTile * e->esize);
   e->tpad = (S - 1) * kLayoutTile;
   return FCX_OK;
@@ -2013,59 +2052,43 @@ static void stage_setup(fcx_engine *e) {
   if (!e->staging) return;
   const size_t es = e->esize;
   std::vector<StagePool> cand;
-  for (void *p : e->tiled_pools)
-    cand.push_back(StagePool{(char *)p, nullptr, e->tiled_bytes, true, (size_t)kLayoutTile * es,
+  for (auto &p : e->tiled_pools)
+    cand.push_back(StagePool{(char *)p.p, nullptr, e->tiled_bytes, true, (size_t)kLayoutTile * es,
                              (size_t)(kLayoutTile + e->tpad) * es});
-  if (e->pool) cand.push_back(StagePool{(char *)e->pool, nullptr, e->pool_bytes, false, 0, 0});
+  if (e->pool) cand.push_back(StagePool{(char *)e->pool.p, nullptr, e->pool_bytes, false, 0, 0});
   int atm_cand = -1;  // records: the pool the downloads read does not exist yet (atm_unpack)
   if (e->atm_pool) {
     const bool t = e->atm_out_tpad != 0;
     if (e->atm_records) atm_cand = (int)cand.size();
-    cand.push_back(StagePool{e->atm_records ? nullptr : (char *)e->atm_pool, nullptr,
+    cand.push_back(StagePool{e->atm_records ? nullptr : (char *)e->atm_pool.p, nullptr,
                              e->atm_records ? e->atm_soa_bytes : e->atm_pool_bytes, t, t ? (size_t)kLayoutTile * es : 0,
                              t ? (size_t)(kLayoutTile + e->atm_out_tpad) * es : 0});
   }
   for (auto &rm : e->remaps)
-    if (rm.pool) cand.push_back(StagePool{(char *)rm.pool, nullptr, rm.pool_bytes, false, 0, 0});
+    if (rm.pool) cand.push_back(StagePool{(char *)rm.pool.p, nullptr, rm.pool_bytes, false, 0, 0});
   // keep the pools some heap array's mirror lives in
-  auto heap = [&](const void *host, int64_t n) { return host && !lib_block_device_ptr(host, (size_t)std::max<int64_t>(n, 1) * es); };
   std::vector<char> used(cand.size(), 0);
-  auto mark = [&](const void *dev) {
-    for (size_t i = 0; i < cand.size(); ++i)
-      if ((const char *)dev >= cand[i].dev && (const char *)dev < cand[i].dev + cand[i].bytes) used[i] = 1;
-  };
-  for (auto &bf : e->bufs)
-    if (!bf.external && heap(bf.host, bf.n)) mark(bf.dev);
-  for (auto &f : e->atm_fields)
-    if (!f.external && heap(f.out_host, e->n_atmos)) {
-      if (atm_cand >= 0)
-        used[(size_t)atm_cand] = 1;
-      else
-        mark(f.out_dev);
+  for_each_mirror(e, [&](HostMirror &m, MirrorOf kind, size_t) {
+    if (!on_heap(e, m)) return;
+    if (kind == MirrorOf::Atmos && atm_cand >= 0) {  // records: downloaded from the shadow pool
+      used[(size_t)atm_cand] = 1;
+      return;
     }
-  for (auto &rm : e->remaps)
-    for (auto &f : rm.fields)
-      if (!f.external && heap(f.out_host, rm.n_dst)) mark(f.out_dev);
+    for (size_t i = 0; i < cand.size(); ++i)
+      if ((const char *)m.dev >= cand[i].dev && (const char *)m.dev < cand[i].dev + cand[i].bytes) used[i] = 1;
+  });
   for (size_t i = 0; i < cand.size(); ++i)
     if (used[i]) {
       if ((int)i == atm_cand) e->atm_soa_sp = (int)e->spools.size();
       e->spools.push_back(cand[i]);
     }
-  for (auto &bf : e->bufs)
-    if (!bf.external && heap(bf.host, bf.n)) bf.st = stage_ref(e, bf.dev);
-  for (size_t k = 0; k < e->atm_fields.size(); ++k) {
-    auto &f = e->atm_fields[k];
-    if (f.external || !heap(f.out_host, e->n_atmos)) continue;
-    if (e->atm_soa_sp >= 0) {  // field k's slot of the tile-blocked shadow
-      f.st.sp = e->atm_soa_sp;
-      f.st.soff = k * (size_t)kLayoutTile * es;
-    } else {
-      f.st = stage_ref(e, f.out_dev);
-    }
-  }
-  for (auto &rm : e->remaps)
-    for (auto &f : rm.fields)
-      if (!f.external && heap(f.out_host, rm.n_dst)) f.st = stage_ref(e, f.out_dev);
+  for_each_mirror(e, [&](HostMirror &m, MirrorOf kind, size_t k) {
+    if (!on_heap(e, m)) return;
+    if (kind == MirrorOf::Atmos && e->atm_soa_sp >= 0)  // field k's slot of the tile-blocked shadow
+      m.st = StageRef{e->atm_soa_sp, k * (size_t)kLayoutTile * es};
+    else
+      m.st = stage_ref(e, m.dev);
+  });
 }
 
 // A pool whose image cannot be page-locked (a memory-tight node) takes the direct path: its
@@ -2078,13 +2101,9 @@ static void stage_disable(fcx_engine *e, size_t i) {
   StagePool &p = e->spools[i];
   p.host = nullptr;
   p.disabled = true;
-  auto drop = [&](StageRef &st) {
-    if (st.sp == (int)i) st.sp = -1;
-  };
-  for (auto &bf : e->bufs) drop(bf.st);
-  for (auto &f : e->atm_fields) drop(f.st);
-  for (auto &rm : e->remaps)
-    for (auto &f : rm.fields) drop(f.st);
+  for_each_mirror(e, [&](HostMirror &m, MirrorOf, size_t) {
+    if (m.st.sp == (int)i) m.st.sp = -1;
+  });
 }
 
 // FCX_TEST_PIN_FAIL (tests only): 1 = every image fails at commit, as on a node out of
@@ -2131,11 +2150,9 @@ static void stage_prepare_bufs(fcx_engine *e, const std::vector<int> &ids) {
   }
 }
 static void stage_prepare_outputs(fcx_engine *e) {
-  for (auto &f : e->atm_fields)
-    if (f.st.sp >= 0) (void)stage_pin(e, (size_t)f.st.sp, true);
-  for (auto &rm : e->remaps)
-    for (auto &f : rm.fields)
-      if (f.st.sp >= 0) (void)stage_pin(e, (size_t)f.st.sp, true);
+  for_each_output(e, [&](OutField &f, MirrorOf, size_t) {
+    if (f.m.st.sp >= 0) (void)stage_pin(e, (size_t)f.m.st.sp, true);
+  });
 }
 
 // the host images of the pools these transfers use (stage_prepare_* ran before the transfer
@@ -2303,28 +2320,14 @@ static Xfer xfer_of(const StageRef &st, void *host, int64_t n) {
 static int map_staged(fcx_engine *e, int *count) {
   *count = 0;
   const size_t es = e->esize;
-  auto heap = [&](const void *h, int64_t n) { return h && !lib_block_device_ptr(h, (size_t)std::max<int64_t>(n, 1) * es); };
-  auto span = [&](int64_t n) { return ((size_t)std::max<int64_t>(n, 1) * es + 255) / 256 * 256; };
-  struct Item {
-    double **dev;
-    bool *ext;
-    StageRef *st;
-    int64_t n;
-    size_t off;
-  };
-  std::vector<Item> items;
+  auto span = [&](int64_t n) { return (mirror_bytes(n, es) + 255) / 256 * 256; };
+  std::vector<HostMirror *> items;
   size_t total = 0;
-  auto add = [&](double **dev, bool *ext, StageRef *st, int64_t n) {
-    items.push_back(Item{dev, ext, st, n, total});
-    total += span(n);
-  };
-  for (auto &bf : e->bufs)
-    if (!bf.external && heap(bf.host, bf.n)) add(&bf.dev, &bf.external, &bf.st, bf.n);
-  for (auto &f : e->atm_fields)
-    if (!f.external && heap(f.out_host, e->n_atmos)) add(&f.out_dev, &f.external, &f.st, std::max<int64_t>(e->n_atmos, 0));
-  for (auto &rm : e->remaps)
-    for (auto &f : rm.fields)
-      if (!f.external && heap(f.out_host, rm.n_dst)) add(&f.out_dev, &f.external, &f.st, rm.n_dst);
+  for_each_mirror(e, [&](HostMirror &m, MirrorOf, size_t) {
+    if (!on_heap(e, m)) return;
+    items.push_back(&m);
+    total += span(m.n);
+  });
   if (items.empty()) return FCX_OK;
   StagePool p;
   void *h = nullptr, *d = nullptr;
@@ -2341,12 +2344,13 @@ static int map_staged(fcx_engine *e, int *count) {
   p.mapped = true;
   const int sp = (int)e->spools.size();
   e->spools.push_back(p);
-  for (const Item &it : items) {
-    *it.dev = reinterpret_cast<double *>(p.dev + it.off);
-    *it.ext = true;  // no engine mirror: the kernels use the image
-    it.st->sp = sp;
-    it.st->soff = it.off;
-    e->zc_bytes += it.n * (int64_t)es;
+  size_t off = 0;
+  for (HostMirror *m : items) {
+    m->dev = reinterpret_cast<double *>(p.dev + off);
+    m->external = true;  // no engine mirror: the kernels use the image
+    m->st = StageRef{sp, off};
+    e->zc_bytes += m->n * (int64_t)es;
+    off += span(m->n);
   }
   for (auto &bf : e->bufs)
     if (bf.st.sp == sp) bf.in_place = true;
@@ -2396,9 +2400,9 @@ static double remap_scatter(const fcx_engine::Remap &rm) {
   int64_t links = 0, distinct = 0;
   std::vector<int32_t> seg;
   for (int64_t b = 0; b < nb; b += every) {
-    const int32_t k0 = rm.row[(size_t)(b * 256)], k1 = rm.row[(size_t)std::min<int64_t>(rm.n_dst, (b + 1) * 256)];
+    const int32_t k0 = rm.map.row[(size_t)(b * 256)], k1 = rm.map.row[(size_t)std::min<int64_t>(rm.n_dst, (b + 1) * 256)];
     seg.clear();
-    for (int32_t k = k0; k < k1; ++k) seg.push_back(rm.col[(size_t)k] >> 3);
+    for (int32_t k = k0; k < k1; ++k) seg.push_back(rm.map.col[(size_t)k] >> 3);
     std::sort(seg.begin(), seg.end());
     distinct += std::unique(seg.begin(), seg.end()) - seg.begin();
     links += k1 - k0;
@@ -2406,16 +2410,13 @@ static double remap_scatter(const fcx_engine::Remap &rm) {
   return links ? (double)distinct / (double)links : 0.0;
 }
 
-extern "C" int fcx_commit(fcx_engine *e) {
-  if (!e) return fail(FCX_E_ARG, "NULL engine");
-  if (e->committed) return FCX_OK;
-  if (int r = validate(e)) return r;
-  bool any_constant = false;
-  for (auto &bf : e->bufs) any_constant = any_constant || bf.constant;
-  decide_uniform(e);
-  if (any_constant)  // a constant some plan would write is an error here, not at that plan's first run
-    if (int r = plan_check_all(e, true)) return r;
-  if (int r = gpu_init(e)) return r;
+// ---- fcx_commit, step by step (in the order fcx_commit calls them)
+
+// which transport moves every host array: in place, a span, or (the rest) a mirror
+static int commit_transports(fcx_engine *e) {
+  for_each_output(e, [&](OutField &f, MirrorOf kind, size_t k) {
+    f.m.n = kind == MirrorOf::Atmos ? e->n_atmos : e->remaps[k].n_dst;
+  });
   // Zero-copy of fcx_host_malloc arrays.  2 (auto, default): where the pipelined step would
   // not apply (grids below two chunks, where the step is latency-bound and per-array copies
   // dominate it); 1: at any size; 0: never.  Caller heap arrays always take mirrors.
@@ -2437,6 +2438,11 @@ extern "C" int fcx_commit(fcx_engine *e) {
     if (int r = map_lib_spans(e, &spanned)) return r;
   }
   classify_written(e);
+  return FCX_OK;
+}
+
+// the field mirrors: tile-blocked pools, or one pooled allocation
+static int commit_field_pools(fcx_engine *e) {
   bool any_external = false;
   for (auto &bf : e->bufs) any_external = any_external || bf.external;
   if (e->tiled_opt && !any_external && !e->bufs.empty()) {
@@ -2454,197 +2460,178 @@ extern "C" int fcx_commit(fcx_engine *e) {
   }
   if (total) {
     e->pool_bytes = total;
-    hipError_t err = hipMalloc(&e->pool, total);
+    hipError_t err = e->pool.alloc(total);
     if (err != hipSuccess)
       return fail(FCX_E_NOMEM, "hipMalloc(%zu) for the field mirrors: %s", total, hipGetErrorString(err));
     for (size_t b = 0; b < e->bufs.size(); ++b)
-      if (!e->bufs[b].external) e->bufs[b].dev = reinterpret_cast<double *>((char *)e->pool + off[b]);
+      if (!e->bufs[b].external) e->bufs[b].dev = reinterpret_cast<double *>((char *)e->pool.p + off[b]);
   }
-  // the constants' mirrors: filled once, in the mirrors' layout, and only read from here on
+  return FCX_OK;
+}
+
+// the constants' mirrors: filled once, in the mirrors' layout, and only read from here on
+static int commit_constants(fcx_engine *e) {
+  bool any_constant = false;
   for (auto &bf : e->bufs) {
+    any_constant = any_constant || bf.constant;
     // read outside the flux pass (a regrid source, an averaged, accumulated or remapped field):
     // filled now; a uniform one when a plan streams it or fcx_device_ptr asks for it
     if (!bf.constant || bf.uniform) continue;
     if (int r = fill_constant(e, bf)) return r;
   }
   if (any_constant) HIP_TRY(hipStreamSynchronize(e->stream));
-  if (e->lcorr) {
-    HIP_TRY(hipMalloc(&e->corr_dev, std::max<size_t>(e->corr_mm.size(), 1) * e->esize));
-    if (e->f32) {  // rounded once; the fp32 kernels add them in fp32
-      std::vector<float> cf(e->corr_mm.begin(), e->corr_mm.end());
-      HIP_TRY(hipMemcpy(e->corr_dev, cf.data(), cf.size() * sizeof(float), hipMemcpyHostToDevice));
-    } else {
-      HIP_TRY(hipMemcpy(e->corr_dev, e->corr_mm.data(), e->corr_mm.size() * sizeof(double),
-                        hipMemcpyHostToDevice));
+  return FCX_OK;
+}
+
+// the bias corrections, rounded once for an fp32 engine (whose kernels add them in fp32)
+static int commit_corrections(fcx_engine *e) {
+  if (!e->lcorr) return FCX_OK;
+  if (e->f32) return e->corr_dev.upload(std::vector<float>(e->corr_mm.begin(), e->corr_mm.end()));
+  return e->corr_dev.upload(e->corr_mm);
+}
+
+// the compacted atmosphere map, and the first cell's atmosphere cell of every wave tile: the
+// crossing records' entry, where launches with records read the compacted map
+static int commit_compact_map(fcx_engine *e) {
+  const int64_t nx = (int64_t)e->atm_idx.size(), nw = (nx + 31) / 32;
+  std::vector<uint32_t> seg((size_t)(2 * nw + 1), 0u);  // bits, then prefix counts (int32)
+  std::vector<int32_t> atm;
+  for (int64_t x = 0; x < nx; ++x)
+    if (x == 0 || e->atm_idx[(size_t)x] != e->atm_idx[(size_t)x - 1]) {
+      seg[(size_t)(x >> 5)] |= 1u << (x & 31);
+      atm.push_back(e->atm_idx[(size_t)x]);
     }
+  int32_t run = 0;
+  for (int64_t w = 0; w <= nw; ++w) {
+    seg[(size_t)(nw + w)] = (uint32_t)run;
+    if (w < nw) run += __builtin_popcount(seg[(size_t)w]);
   }
-  for (auto &c : e->rg) {
-    if (!c.set) continue;
-    HIP_TRY(hipMalloc(&c.d_row, c.row_ptr.size() * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&c.d_col, std::max<size_t>(c.col.size(), 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&c.d_w, std::max<size_t>(c.w.size(), 1) * sizeof(double)));
-    HIP_TRY(hipMemcpy(c.d_row, c.row_ptr.data(), c.row_ptr.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (!c.col.empty()) {
-      HIP_TRY(hipMemcpy(c.d_col, c.col.data(), c.col.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      if (e->f32) {  // REAL(wp) weights of the single-precision build: rounded once
-        std::vector<float> wf(c.w.begin(), c.w.end());
-        HIP_TRY(hipMemcpy(c.d_w, wf.data(), wf.size() * sizeof(float), hipMemcpyHostToDevice));
-      } else {
-        HIP_TRY(hipMemcpy(c.d_w, c.w.data(), c.w.size() * sizeof(double), hipMemcpyHostToDevice));
-      }
-    }
+  e->atm_seg_words = nw;
+  e->atm_segments = (int64_t)atm.size();
+  const size_t head = seg.size() * sizeof(uint32_t);
+  HIP_TRY(e->d_atm_seg.alloc(head + std::max<size_t>(atm.size(), 1) * sizeof(int32_t)));
+  HIP_TRY(hipMemcpy(e->d_atm_seg, seg.data(), head, hipMemcpyHostToDevice));
+  if (!atm.empty())
+    HIP_TRY(hipMemcpy((char *)e->d_atm_seg.p + head, atm.data(), atm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  if (!compact_map(e->f32, false)) return FCX_OK;
+  const int64_t tc = (int64_t)(e->f32 ? kF32Cpl : 2) * 64, nt = (nx + tc - 1) / tc;
+  std::vector<int32_t> a0((size_t)nt);
+  for (int64_t t = 0; t < nt; ++t) a0[(size_t)t] = e->atm_idx[(size_t)(t * tc)];
+  return e->d_atm_tile_a0.upload(a0);
+}
+
+// the regrid matrices and the atmosphere map, with what the fused accumulation reads of it
+static int commit_maps(fcx_engine *e) {
+  for (auto &c : e->rg)
+    if (c.set)  // (REAL(wp) weights of the single-precision build)
+      if (int r = c.upload(e->f32)) return r;
+  if (e->n_atmos < 0) return FCX_OK;
+  if (int r = e->atm.upload(false, !e->atm_contiguous)) return r;
+  if (!e->atm_contiguous || e->atm_idx.empty()) return FCX_OK;
+  // the per-cell index, where some fp64 launch reads it
+  if (!(compact_map(e->f32, true) && compact_map(e->f32, false)))
+    if (int r = e->d_atm_idx.upload(e->atm_idx)) return r;
+  // the compacted map, where some launch reads it
+  if (compact_map(e->f32, true) || compact_map(e->f32, false))
+    if (int r = commit_compact_map(e)) return r;
+  // the fused path's crossing records
+  const int64_t tiles = (e->n[0] + kTile - 1) / kTile;
+  HIP_TRY(e->d_atm_xrec.alloc((size_t)std::max<int64_t>(tiles, 1) * kXRec * sizeof(double)));
+  // tile boundaries a segment runs across: none (a map whose runs never cross a wave
+  // tile) means no fix-up launch at all
+  e->atm_crossings = 0;
+  for (size_t b = kTile; b < e->atm_idx.size(); b += kTile) e->atm_crossings += e->atm_idx[b - 1] == e->atm_idx[b];
+  if (!e->atm_empty.empty())
+    if (int r = e->d_atm_empty.upload(e->atm_empty)) return r;
+  return FCX_OK;
+}
+
+// the atmosphere outputs' mirrors: tile-blocked, per-cell records, or one array after the other
+static int commit_atmos_outputs(fcx_engine *e) {
+  if (e->n_atmos < 0) return FCX_OK;
+  size_t need = 0;
+  bool atm_ext = false;
+  for (auto &f : e->atm_fields) {
+    atm_ext = atm_ext || f.m.external;
+    if (!f.m.external) need += (mirror_bytes(f.m.n, e->esize) + 255) / 256 * 256;
   }
-  if (e->n_atmos >= 0) {
-    HIP_TRY(hipMalloc(&e->d_atm_row, e->atm_row.size() * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(e->d_atm_row, e->atm_row.data(), e->atm_row.size() * sizeof(int32_t),
-                      hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&e->d_atm_w, std::max<size_t>(e->atm_w.size(), 1) * sizeof(double)));
-    if (!e->atm_w.empty())
-      HIP_TRY(hipMemcpy(e->d_atm_w, e->atm_w.data(), e->atm_w.size() * sizeof(double), hipMemcpyHostToDevice));
-    // the per-cell index, where some fp64 launch reads it
-    if (e->atm_contiguous && !e->atm_idx.empty() && !(compact_map(e->f32, true) && compact_map(e->f32, false))) {
-      HIP_TRY(hipMalloc(&e->d_atm_idx, e->atm_idx.size() * sizeof(int32_t)));
-      HIP_TRY(hipMemcpy(e->d_atm_idx, e->atm_idx.data(), e->atm_idx.size() * sizeof(int32_t),
-                        hipMemcpyHostToDevice));
-    }
-    // the compacted map, where some launch reads it
-    if (e->atm_contiguous && !e->atm_idx.empty() && (compact_map(e->f32, true) || compact_map(e->f32, false))) {
-      const int64_t nx = (int64_t)e->atm_idx.size(), nw = (nx + 31) / 32;
-      std::vector<uint32_t> seg((size_t)(2 * nw + 1), 0u);  // bits, then prefix counts (int32)
-      std::vector<int32_t> atm;
-      for (int64_t x = 0; x < nx; ++x)
-        if (x == 0 || e->atm_idx[(size_t)x] != e->atm_idx[(size_t)x - 1]) {
-          seg[(size_t)(x >> 5)] |= 1u << (x & 31);
-          atm.push_back(e->atm_idx[(size_t)x]);
-        }
-      int32_t run = 0;
-      for (int64_t w = 0; w <= nw; ++w) {
-        seg[(size_t)(nw + w)] = (uint32_t)run;
-        if (w < nw) run += __builtin_popcount(seg[(size_t)w]);
-      }
-      e->atm_seg_words = nw;
-      e->atm_segments = (int64_t)atm.size();
-      const size_t head = seg.size() * sizeof(uint32_t);
-      HIP_TRY(hipMalloc(&e->d_atm_seg, head + std::max<size_t>(atm.size(), 1) * sizeof(int32_t)));
-      HIP_TRY(hipMemcpy(e->d_atm_seg, seg.data(), head, hipMemcpyHostToDevice));
-      if (!atm.empty())
-        HIP_TRY(hipMemcpy((char *)e->d_atm_seg + head, atm.data(), atm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      // the first cell's atmosphere cell of every wave tile: the crossing records' entry, where
-      // launches with records read the compacted map
-      if (compact_map(e->f32, false)) {
-        const int64_t tc = (int64_t)(e->f32 ? kF32Cpl : 2) * 64, nt = (nx + tc - 1) / tc;
-        std::vector<int32_t> a0((size_t)nt);
-        for (int64_t t = 0; t < nt; ++t) a0[(size_t)t] = e->atm_idx[(size_t)(t * tc)];
-        HIP_TRY(hipMalloc(&e->d_atm_tile_a0, (size_t)std::max<int64_t>(nt, 1) * sizeof(int32_t)));
-        if (nt) HIP_TRY(hipMemcpy(e->d_atm_tile_a0, a0.data(), a0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      }
-    }
-    if (e->atm_contiguous && !e->atm_idx.empty()) {  // the fused path's crossing records
-      const int64_t tiles = (e->n[0] + kTile - 1) / kTile;
-      HIP_TRY(hipMalloc(&e->d_atm_xrec, (size_t)std::max<int64_t>(tiles, 1) * kXRec * sizeof(double)));
-      // tile boundaries a segment runs across: none (a map whose runs never cross a wave
-      // tile) means no fix-up launch at all
-      e->atm_crossings = 0;
-      for (size_t b = kTile; b < e->atm_idx.size(); b += kTile) e->atm_crossings += e->atm_idx[b - 1] == e->atm_idx[b];
-      if (!e->atm_empty.empty()) {
-        HIP_TRY(hipMalloc(&e->d_atm_empty, e->atm_empty.size() * sizeof(int32_t)));
-        HIP_TRY(hipMemcpy(e->d_atm_empty, e->atm_empty.data(), e->atm_empty.size() * sizeof(int32_t),
-                          hipMemcpyHostToDevice));
-      }
-    }
-    if (!e->atm_contiguous) {
-      HIP_TRY(hipMalloc(&e->d_atm_col, std::max<size_t>(e->atm_col.size(), 1) * sizeof(int32_t)));
-      if (!e->atm_col.empty())
-        HIP_TRY(hipMemcpy(e->d_atm_col, e->atm_col.data(), e->atm_col.size() * sizeof(int32_t),
-                          hipMemcpyHostToDevice));
-    }
-    size_t need = 0;
-    bool atm_ext = false;
-    for (auto &f : e->atm_fields) {
-      atm_ext = atm_ext || f.external;
-      if (!f.external) need += ((size_t)std::max<int64_t>(e->n_atmos, 1) * e->esize + 255) / 256 * 256;
-    }
-    // tile-blocked outputs (with the field mirrors, FCX_TILED_ATM): the fields' tiles of 4096
-    // atmosphere cells side by side, so the fused kernel's segment-end stores of a wave land
-    // in one region instead of one per field
-    const int64_t nfa = (int64_t)e->atm_fields.size();
-    if (FCX_TILED_ATM && e->tpad && !atm_ext && nfa >= 2 && e->n_atmos > 0) {
-      const int64_t tiles = (e->n_atmos + kLayoutTile - 1) / kLayoutTile;
-      const size_t soa_bytes = (size_t)tiles * nfa * kLayoutTile * e->esize;
-      e->atm_out_tpad = (nfa - 1) * kLayoutTile;
-      need = 0;
-      // Per-cell records instead (FCX_OPT_ATM_RECORDS): fp64, engine-owned outputs.  The
-      // tile-blocked pool is then the downloads' shadow, allocated at the first download
-      // (atm_unpack), and the kernels write the records.  Auto: where the whole-grid launch is
-      // the halo launch that stores a wave's records as one dense run (one surface type, the
-      // six fluxes, a map with crossings whose segments the halo covers: full_range_halo) --
-      // every other launch stores the records value by value at a 48-B stride, which measured
-      // far slower than the arrays (periodic map, no crossings: 1.097 against 0.712 ms per group
-      // launch, profiles/r07/full/) -- and from two pipeline chunks of exchange cells: below, a
-      // step is dispatch-bound and downloads every time, and the unpack launch before the
-      // download would cost it more than the kernel gains.
-      const int halo_h = (e->atm_maxseg - 1 + 1) / 2;
-      const bool dense_launch = e->T == 1 && nfa == kFusedFields && e->atm_contiguous && e->atm_halo &&
-                                e->atm_crossings > 0 && halo_h >= 1 && halo_h <= 4;
-      e->atm_records = !e->f32 && (e->atm_records_opt == 1 ||
-                                   (e->atm_records_opt == 2 && dense_launch && e->n[0] >= 2 * e->min_chunk));
-      if (e->atm_records) {
-        e->atm_soa_bytes = soa_bytes;
-        e->atm_pool_bytes = ((size_t)e->n_atmos * nfa * sizeof(double) + 255) / 256 * 256;
-        HIP_TRY(hipMalloc(&e->atm_pool, e->atm_pool_bytes));
-        for (int64_t k = 0; k < nfa; ++k) e->atm_fields[k].out_dev = reinterpret_cast<double *>(e->atm_pool) + k;
-      } else {
-        e->atm_pool_bytes = soa_bytes;
-        HIP_TRY(hipMalloc(&e->atm_pool, e->atm_pool_bytes));
-        for (int64_t k = 0; k < nfa; ++k)
-          e->atm_fields[k].out_dev = reinterpret_cast<double *>((char *)e->atm_pool + (size_t)k * kLayoutTile * e->esize);
-      }
-    }
-    if (need) {
-      e->atm_pool_bytes = need;
-      HIP_TRY(hipMalloc(&e->atm_pool, need));
-      size_t off = 0;
-      for (auto &f : e->atm_fields)
-        if (!f.external) {
-          f.out_dev = reinterpret_cast<double *>((char *)e->atm_pool + off);
-          off += ((size_t)std::max<int64_t>(e->n_atmos, 1) * e->esize + 255) / 256 * 256;
-        }
-    }
+  // tile-blocked outputs (with the field mirrors, FCX_TILED_ATM): the fields' tiles of 4096
+  // atmosphere cells side by side, so the fused kernel's segment-end stores of a wave land
+  // in one region instead of one per field
+  const int64_t nfa = (int64_t)e->atm_fields.size();
+  if (FCX_TILED_ATM && e->tpad && !atm_ext && nfa >= 2 && e->n_atmos > 0) {
+    const int64_t tiles = (e->n_atmos + kLayoutTile - 1) / kLayoutTile;
+    const size_t soa_bytes = (size_t)tiles * nfa * kLayoutTile * e->esize;
+    e->atm_out_tpad = (nfa - 1) * kLayoutTile;
+    // Per-cell records instead (FCX_OPT_ATM_RECORDS): fp64, engine-owned outputs.  The
+    // tile-blocked pool is then the downloads' shadow, allocated at the first download
+    // (atm_unpack), and the kernels write the records.  Auto: where the whole-grid launch is
+    // the halo launch that stores a wave's records as one dense run (one surface type, the
+    // six fluxes, a map with crossings whose segments the halo covers: full_range_halo) --
+    // every other launch stores the records value by value at a 48-B stride, which measured
+    // far slower than the arrays (periodic map, no crossings: 1.097 against 0.712 ms per group
+    // launch, profiles/r07/full/) -- and from two pipeline chunks of exchange cells: below, a
+    // step is dispatch-bound and downloads every time, and the unpack launch before the
+    // download would cost it more than the kernel gains.
+    const int halo_h = (e->atm_maxseg - 1 + 1) / 2;
+    const bool dense_launch = e->T == 1 && nfa == kFusedFields && e->atm_contiguous && e->atm_halo &&
+                              e->atm_crossings > 0 && halo_h >= 1 && halo_h <= 4;
+    e->atm_records = !e->f32 && (e->atm_records_opt == 1 ||
+                                 (e->atm_records_opt == 2 && dense_launch && e->n[0] >= 2 * e->min_chunk));
+    if (e->atm_records) e->atm_soa_bytes = soa_bytes;
+    e->atm_pool_bytes = e->atm_records ? ((size_t)e->n_atmos * nfa * sizeof(double) + 255) / 256 * 256 : soa_bytes;
+    HIP_TRY(e->atm_pool.alloc(e->atm_pool_bytes));
+    for (int64_t k = 0; k < nfa; ++k)  // field k: its column of the records, or its slot of the first tile
+      e->atm_fields[k].m.dev = e->atm_records
+                                   ? reinterpret_cast<double *>(e->atm_pool.p) + k
+                                   : reinterpret_cast<double *>((char *)e->atm_pool.p + (size_t)k * kLayoutTile * e->esize);
+    return FCX_OK;
   }
-  if (e->own_shared && e->n_atmos >= 0) {  // [n_boundaries][fields] slots, zero on entry
-    const size_t stride = std::max<size_t>(e->atm_fields.size(), 1);
-    const size_t cnt = std::max<size_t>((size_t)e->atm_nb * stride, 1);
-    HIP_TRY(hipMalloc(&e->atm_shared_own, cnt * sizeof(double)));
-    HIP_TRY(hipMemset(e->atm_shared_own, 0, cnt * sizeof(double)));
-    if (e->atm_left >= 0 && e->atm_right >= 0 && e->n_atmos < 2 && e->atm_left != e->atm_right)
-      return fail(FCX_E_ARG, "the one atmosphere cell is shared on both sides: it needs one boundary slot for all "
-                             "its ranks (left == right), not %d and %d", e->atm_left, e->atm_right);
-    e->atm_shared = e->atm_nb > 0 ? e->atm_shared_own : nullptr;
-    e->atm_stride = (int32_t)stride;
-  }
+  if (!need) return FCX_OK;
+  e->atm_pool_bytes = need;
+  HIP_TRY(e->atm_pool.alloc(need));
+  size_t off = 0;
+  for (auto &f : e->atm_fields)
+    if (!f.m.external) {
+      f.m.dev = reinterpret_cast<double *>((char *)e->atm_pool.p + off);
+      off += (mirror_bytes(f.m.n, e->esize) + 255) / 256 * 256;
+    }
+  return FCX_OK;
+}
+
+// fcx_set_atmos_boundaries: the engine's own [n_boundaries][fields] slots, zero on entry
+static int commit_shared_slots(fcx_engine *e) {
+  if (!e->own_shared || e->n_atmos < 0) return FCX_OK;
+  const size_t stride = std::max<size_t>(e->atm_fields.size(), 1);
+  const size_t cnt = std::max<size_t>((size_t)e->atm_nb * stride, 1);
+  HIP_TRY(e->atm_shared_own.alloc(cnt * sizeof(double)));
+  HIP_TRY(hipMemset(e->atm_shared_own, 0, cnt * sizeof(double)));
+  if (e->atm_left >= 0 && e->atm_right >= 0 && e->n_atmos < 2 && e->atm_left != e->atm_right)
+    return fail(FCX_E_ARG, "the one atmosphere cell is shared on both sides: it needs one boundary slot for all "
+                           "its ranks (left == right), not %d and %d", e->atm_left, e->atm_right);
+  e->atm_shared = e->atm_nb > 0 ? e->atm_shared_own.p : nullptr;
+  e->atm_stride = (int32_t)stride;
+  return FCX_OK;
+}
+
+// every remap's map, its outputs' mirrors, and the records scratch the packed gathers share
+static int commit_remaps(fcx_engine *e) {
   for (auto &rm : e->remaps) {
     for (auto &f : rm.fields)
       if (rm.max_src >= e->n[f.g - 1])
         return fail(FCX_E_ARG, "remap link source %d outside the %lld cells of grid %d", rm.max_src,
                     (long long)e->n[f.g - 1], f.g);
-    HIP_TRY(hipMalloc(&rm.d_row, rm.row.size() * sizeof(int32_t)));
-    HIP_TRY(hipMemcpy(rm.d_row, rm.row.data(), rm.row.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIP_TRY(hipMalloc(&rm.d_col, std::max<size_t>(rm.col.size(), 1) * sizeof(int32_t)));
-    HIP_TRY(hipMalloc(&rm.d_w, std::max<size_t>(rm.w.size(), 1) * sizeof(double)));
-    if (!rm.col.empty()) {
-      HIP_TRY(hipMemcpy(rm.d_col, rm.col.data(), rm.col.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-      HIP_TRY(hipMemcpy(rm.d_w, rm.w.data(), rm.w.size() * sizeof(double), hipMemcpyHostToDevice));
-    }
-    const size_t one = ((size_t)std::max<int64_t>(rm.n_dst, 1) * e->esize + 255) / 256 * 256;
+    if (int r = rm.map.upload(false)) return r;
+    const size_t one = (mirror_bytes(rm.n_dst, e->esize) + 255) / 256 * 256;
     size_t need = 0;
-    for (auto &f : rm.fields) need += f.external ? 0 : one;
+    for (auto &f : rm.fields) need += f.m.external ? 0 : one;
     if (need) {
       rm.pool_bytes = need;
-      HIP_TRY(hipMalloc(&rm.pool, need));
+      HIP_TRY(rm.pool.alloc(need));
       size_t off = 0;
       for (auto &f : rm.fields)
-        if (!f.external) {
-          f.out_dev = reinterpret_cast<double *>((char *)rm.pool + off);
+        if (!f.m.external) {
+          f.m.dev = reinterpret_cast<double *>((char *)rm.pool.p + off);
           off += one;
         }
     }
@@ -2659,7 +2646,13 @@ extern "C" int fcx_commit(fcx_engine *e) {
     if (remap_packs(e, rm, (int)nf_max))
       e->rec_bytes = std::max(e->rec_bytes, (size_t)(rm.max_src + 1) * rec_width(e, (int)nf_max) * e->esize);
   }
-  if (e->rec_bytes) HIP_TRY(hipMalloc(&e->d_rec, e->rec_bytes));
+  if (e->rec_bytes) HIP_TRY(e->d_rec.alloc(e->rec_bytes));
+  return FCX_OK;
+}
+
+// the staging arena of the mirrors on caller heap arrays (the engine counts as committed
+// here: the whole-step plan is built to see what a step transfers)
+static int commit_staging(fcx_engine *e) {
   stage_setup(e);
   e->committed = true;
   // the pools a whole step transfers are page-locked now, the others at first use
@@ -2673,13 +2666,26 @@ extern "C" int fcx_commit(fcx_engine *e) {
     } else {
       std::fill(eager.begin(), eager.end(), 1);
     }
-    for (auto &f : e->atm_fields)
-      if (f.st.sp >= 0) eager[(size_t)f.st.sp] = 1;
-    for (auto &rm : e->remaps)
-      for (auto &f : rm.fields)
-        if (f.st.sp >= 0) eager[(size_t)f.st.sp] = 1;
+    for_each_output(e, [&](OutField &f, MirrorOf, size_t) {
+      if (f.m.st.sp >= 0) eager[(size_t)f.m.st.sp] = 1;
+    });
   }
   stage_alloc_all(e, eager);
+  return FCX_OK;
+}
+
+extern "C" int fcx_commit(fcx_engine *e) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (e->committed) return FCX_OK;
+  if (int r = validate(e)) return r;
+  decide_uniform(e);
+  // a constant some plan would write is an error here, not at that plan's first run
+  if (std::any_of(e->bufs.begin(), e->bufs.end(), [](const Buffer &bf) { return bf.constant; }))
+    if (int r = plan_check_all(e, true)) return r;
+  if (int r = gpu_init(e)) return r;
+  for (auto step : {commit_transports, commit_field_pools, commit_constants, commit_corrections, commit_maps,
+                    commit_atmos_outputs, commit_shared_slots, commit_remaps, commit_staging})
+    if (int r = step(e)) return r;
   return FCX_OK;
 }
 
@@ -2703,7 +2709,7 @@ static const double *month_slice(fcx_engine *e, int32_t t, int *rc) {
   if (!e->lcorr) return nullptr;
   int32_t m = 0;
   if ((*rc = fcx_current_month(e->init_date, t, &m)) != FCX_OK) return nullptr;
-  return reinterpret_cast<const double *>((const char *)e->corr_dev + (size_t)(m - 1) * e->n[0] * e->esize);
+  return reinterpret_cast<const double *>((const char *)e->corr_dev.p + (size_t)(m - 1) * e->n[0] * e->esize);
 }
 
 // the mirrors of buffers `ids` <-> their host arrays on the engine stream: caller heap arrays
@@ -2831,7 +2837,7 @@ static hipError_t get_atm(const fcx_engine *e, double *host, const double *dev, 
 static int atm_unpack(fcx_engine *e, hipStream_t s);
 static const double *atm_src(const fcx_engine *e, size_t k);
 static int run_remaps(fcx_engine *e, int phase);
-static int download_remaps(fcx_engine *e, int phase, hipStream_t s, std::vector<Xfer> *xs);
+static int download_outputs(fcx_engine *e, int phase, hipStream_t s, std::vector<Xfer> *xs, bool atmos = true);
 
 // the reference step order with do_regridding after each calc (flux_calculator.F90:972-991)
 static int staged_sequence(int phase, std::vector<std::pair<uint32_t, int>> &seq) {
@@ -2882,7 +2888,7 @@ static int upload_one(fcx_engine *e, int b) {
       HIP_TRY(stage_dma(e, xs, 0, -1, true, e->stream));
       u.dma = true;
     }
-  } else if (!bf.external || bf.span >= 0) {
+  } else if (bf.moves_over_link()) {
     HIP_TRY(copy_cells(e, bf, 0, bf.n, true, e->stream));
   }
   return FCX_OK;
@@ -2990,20 +2996,7 @@ extern "C" int fcx_download(fcx_engine *e, int phase) {
   stage_prepare_outputs(e);
   std::vector<Xfer> xs;  // every staged download of the phase in one set of DMAs
   std::vector<int> ids = pl->writes;
-  bool any_atm = false;
-  for (auto &f : e->atm_fields) any_atm = any_atm || (f.phase & phase);
-  if (any_atm)
-    if (int r = atm_unpack(e, e->stream)) return r;
-  for (size_t k = 0; k < e->atm_fields.size(); ++k) {
-    auto &f = e->atm_fields[k];
-    if ((f.phase & phase) && e->n_atmos > 0) {
-      if (f.st.sp >= 0)
-        xs.push_back(xfer_of(f.st, f.out_host, e->n_atmos));
-      else if (!f.external)
-        HIP_TRY(get_atm(e, f.out_host, atm_src(e, k), e->stream));
-    }
-  }
-  if (int r = download_remaps(e, phase, e->stream, &xs)) return r;
+  if (int r = download_outputs(e, phase, e->stream, &xs)) return r;
   if (e->any_regrid) {  // device-side regrid destinations of the fields this phase computes
     std::vector<int> extra;
     std::vector<int> vars;
@@ -3044,26 +3037,26 @@ static hipError_t get_atm(const fcx_engine *e, double *host, const double *dev, 
 static int atm_unpack(fcx_engine *e, hipStream_t s) {
   if (!e->atm_records || e->n_atmos <= 0) return FCX_OK;
   if (!e->atm_soa) {
-    HIP_TRY(hipMalloc(&e->atm_soa, e->atm_soa_bytes));
-    if (e->atm_soa_sp >= 0) e->spools[(size_t)e->atm_soa_sp].dev = reinterpret_cast<char *>(e->atm_soa);
+    HIP_TRY(e->atm_soa.alloc(e->atm_soa_bytes));
+    if (e->atm_soa_sp >= 0) e->spools[(size_t)e->atm_soa_sp].dev = reinterpret_cast<char *>(e->atm_soa.p);
   }
-  const int r = launch_atm_unpack(reinterpret_cast<const double *>(e->atm_pool), reinterpret_cast<double *>(e->atm_soa),
+  const int r = launch_atm_unpack(reinterpret_cast<const double *>(e->atm_pool.p), reinterpret_cast<double *>(e->atm_soa.p),
                                   e->n_atmos, (int)e->atm_fields.size(), e->atm_out_tpad, s);
   if (r) return fail(FCX_E_HIP, "atm_unpack launch: %s", hipGetErrorString((hipError_t)r));
   return FCX_OK;
 }
 // where the downloads read atmosphere field k (after atm_unpack)
 static const double *atm_src(const fcx_engine *e, size_t k) {
-  if (!e->atm_records) return e->atm_fields[k].out_dev;
-  return reinterpret_cast<const double *>(reinterpret_cast<const char *>(e->atm_soa) + k * (size_t)kLayoutTile * e->esize);
+  if (!e->atm_records) return e->atm_fields[k].m.dev;
+  return reinterpret_cast<const double *>(reinterpret_cast<const char *>(e->atm_soa.p) + k * (size_t)kLayoutTile * e->esize);
 }
 
 static AtmosArgs atmos_args(fcx_engine *e, int phase) {
   AtmosArgs a{};
   a.f32 = e->f32 ? 1 : 0;
-  a.row_ptr = e->d_atm_row;
-  a.col = e->atm_contiguous ? nullptr : e->d_atm_col;
-  a.w = e->d_atm_w;
+  a.row_ptr = e->atm.d_row;
+  a.col = e->atm_contiguous ? nullptr : e->atm.d_col.p;
+  a.w = e->atm.d_w;
   a.n_atmos = e->n_atmos;
   a.stride = e->atm_stride;
   a.left = e->atm_left;
@@ -3077,7 +3070,7 @@ static AtmosArgs atmos_args(fcx_engine *e, int phase) {
     const auto &f = e->atm_fields[i];
     if (!(f.phase & phase) || a.nf >= kMaxAtmosFields) continue;
     a.x[a.nf] = e->dptr(f.s, f.g, f.var);
-    a.out[a.nf] = f.out_dev;
+    a.out[a.nf] = f.m.dev;
     a.scol[a.nf] = (int32_t)i;
     ++a.nf;
   }
@@ -3102,9 +3095,9 @@ static int run_remaps(fcx_engine *e, int phase) {
     int gi = 0;
     AtmosArgs a{};
     a.f32 = e->f32 ? 1 : 0;
-    a.row_ptr = rm.d_row;
-    a.col = rm.d_col;
-    a.w = rm.d_w;
+    a.row_ptr = rm.map.d_row;
+    a.col = rm.map.d_col;
+    a.w = rm.map.d_w;
     a.n_atmos = rm.n_dst;
     a.left = a.right = -1;
     a.tpad = e->tpad;
@@ -3133,7 +3126,7 @@ static int run_remaps(fcx_engine *e, int phase) {
     for (auto &f : rm.fields) {
       if (!(f.phase & phase)) continue;
       a.x[a.nf] = e->dptr(f.s, f.g, f.var);
-      a.out[a.nf] = f.out_dev;
+      a.out[a.nf] = f.m.dev;
       if (!a.x[a.nf]) return fail(FCX_E_MISSING, "remap field %s(%d) is not bound", kVarNames[var0(f.var)], f.s);
       if (++a.nf == kMaxAtmosFields)
         if (int r = flush()) return r;
@@ -3143,28 +3136,44 @@ static int run_remaps(fcx_engine *e, int phase) {
   return FCX_OK;
 }
 
-// remap outputs -> host: staged ones appended to xs, the others copied directly
-static int download_remaps(fcx_engine *e, int phase, hipStream_t s, std::vector<Xfer> *xs) {
-  for (auto &rm : e->remaps)
-    for (auto &f : rm.fields)
-      if ((f.phase & phase) && rm.n_dst > 0) {
-        if (f.st.sp >= 0)
-          xs->push_back(xfer_of(f.st, f.out_host, rm.n_dst));
-        else if (!f.external)
-          HIP_TRY(hipMemcpyAsync(f.out_host, f.out_dev, rm.n_dst * e->esize, kD2H, s));
-      }
-  return FCX_OK;
+// the phase's atmosphere (atmos: unless left out) and remap outputs -> host on stream s: staged
+// ones appended to xs, the others copied directly.  Atmosphere records are unpacked first
+// (atm_unpack) and read from their shadow (atm_src).
+static int download_outputs(fcx_engine *e, int phase, hipStream_t s, std::vector<Xfer> *xs, bool atmos) {
+  int rc = FCX_OK;
+  bool unpacked = false;
+  for_each_output(e, [&](OutField &f, MirrorOf kind, size_t k) {
+    const HostMirror &m = f.m;
+    if (rc || !(f.phase & phase) || m.n <= 0 || (kind == MirrorOf::Atmos && !atmos)) return;
+    if (kind == MirrorOf::Atmos && !unpacked) {
+      unpacked = true;
+      if ((rc = atm_unpack(e, s))) return;
+    }
+    if (m.st.sp >= 0) {
+      xs->push_back(xfer_of(m.st, m.host, m.n));
+    } else if (!m.external) {
+      const hipError_t err = kind == MirrorOf::Atmos ? get_atm(e, m.host, atm_src(e, k), s)
+                                                     : hipMemcpyAsync(m.host, m.dev, m.n * e->esize, kD2H, s);
+      if (err != hipSuccess) rc = fail(FCX_E_HIP, "output download: %s", hipGetErrorString(err));
+    }
+  });
+  return rc;
 }
 
-// after the flux launch(es) of fcx_run: the accumulation when it is not fused, the boundary
-// exchange of an attached communicator, the remaps, the closing timing event
-static int run_tail(fcx_engine *e, int phase) {
+// after the flux launch(es) of a run: the accumulation when it is not fused, the boundary
+// exchange of an attached communicator, the remaps
+static int run_outputs(fcx_engine *e, int phase) {
   if (e->atmos_in_run && !e->atm_done_fused)
     if (int r = run_atmos(e, phase)) return r;
   e->atm_done = e->atmos_in_run || e->atm_done_fused;
   if (e->atm_done)
     if (int r = comm_exchange(e)) return r;
-  if (int r = run_remaps(e, phase)) return r;
+  return run_remaps(e, phase);
+}
+
+// ... and fcx_run's closing timing event
+static int run_tail(fcx_engine *e, int phase) {
+  if (int r = run_outputs(e, phase)) return r;
   if (e->timing) HIP_TRY(hipEventRecord(e->ev1, e->stream));
   e->timed = e->timing;
   return FCX_OK;
@@ -3293,7 +3302,7 @@ static void group_members(const GroupLaunchMember *mem, int nm, GroupMember *gm)
     e->rec_written = false;
     fields_taken(e);
     const int64_t own = (m.lc.f32 ? kF32Cpl : 2) * (64 - m.lc.halo);
-    gm[k] = GroupMember{m.pl->dev, m.corr_m, 0, m.lc.variant, 0, m.pl->af};
+    gm[k] = GroupMember{m.pl->dev.p, m.corr_m, 0, m.lc.variant, 0, m.pl->af};
     gm[k].af.n_tiles = (m.pl->host.n_max + own - 1) / own;
   }
 }
@@ -3384,13 +3393,13 @@ static int step_pipelined(fcx_engine *e, int phase, int32_t t, Plan *pl) {
     const Buffer &bf = e->bufs[b];
     if (bf.n == 0) continue;
     if (bf.st.sp >= 0) xin.push_back(xfer_of(bf.st, bf.host, bf.n));
-    else if (!bf.external || bf.span >= 0) din.push_back(b);
+    else if (bf.moves_over_link()) din.push_back(b);
   }
   for (int b : pl->writes) {
     const Buffer &bf = e->bufs[b];
     if (bf.n == 0) continue;
     if (bf.st.sp >= 0) xout.push_back(xfer_of(bf.st, bf.host, bf.n));
-    else if (!bf.external || bf.span >= 0) dout.push_back(b);
+    else if (bf.moves_over_link()) dout.push_back(b);
   }
   if (!xin.empty() || !xout.empty()) {
     if (int r = stage_alloc(e, xin)) return r;
@@ -3443,31 +3452,11 @@ static int step_pipelined(fcx_engine *e, int phase, int32_t t, Plan *pl) {
     if (!xout.empty() && k >= 2)
       if (int r = scatter_upto(k - 1)) return r;  // chunk k-2 has had two chunks' time to land
   }
-  if (e->atmos_in_run && !e->atm_done_fused)
-    if (int r = run_atmos(e, phase)) return r;
-  e->atm_done = e->atmos_in_run || e->atm_done_fused;
-  if (e->atm_done)
-    if (int r = comm_exchange(e)) return r;
-  if (int r = run_remaps(e, phase)) return r;
+  if (int r = run_outputs(e, phase)) return r;
   HIP_TRY(hipEventRecord(e->ev_comp[K - 1], e->stream));
   HIP_TRY(hipStreamWaitEvent(e->s_out, e->ev_comp[K - 1], 0));
-  std::vector<Xfer> xa;  // atmosphere and remap outputs
-  if (e->atmos_in_run || e->atm_done_fused) {
-    bool any_atm = false;
-    for (auto &f : e->atm_fields) any_atm = any_atm || (f.phase & phase);
-    if (any_atm)
-      if (int r = atm_unpack(e, e->s_out)) return r;
-    for (size_t k = 0; k < e->atm_fields.size(); ++k) {
-      auto &f = e->atm_fields[k];
-      if ((f.phase & phase) && e->n_atmos > 0) {
-        if (f.st.sp >= 0)
-          xa.push_back(xfer_of(f.st, f.out_host, e->n_atmos));
-        else if (!f.external)
-          HIP_TRY(get_atm(e, f.out_host, atm_src(e, k), e->s_out));
-      }
-    }
-  }
-  if (int r = download_remaps(e, phase, e->s_out, &xa)) return r;
+  std::vector<Xfer> xa;  // atmosphere (when this step accumulated them) and remap outputs
+  if (int r = download_outputs(e, phase, e->s_out, &xa, e->atm_done)) return r;
   if (!xa.empty()) {
     if (int r = stage_alloc(e, xa)) return r;
     HIP_TRY(stage_dma(e, xa, 0, -1, false, e->s_out));
@@ -3483,10 +3472,9 @@ static int step_pipelined(fcx_engine *e, int phase, int32_t t, Plan *pl) {
 }
 
 static bool host_bound(const fcx_engine *e, const Plan *pl) {
-  for (int b : pl->reads)
-    if (!e->bufs[b].external || e->bufs[b].st.sp >= 0 || e->bufs[b].span >= 0) return true;
-  for (int b : pl->writes)
-    if (!e->bufs[b].external || e->bufs[b].st.sp >= 0 || e->bufs[b].span >= 0) return true;
+  for (const std::vector<int> *ids : {&pl->reads, &pl->writes})
+    for (int b : *ids)
+      if (e->bufs[b].moves_over_link()) return true;
   return false;
 }
 
@@ -3767,10 +3755,6 @@ extern "C" int fcx_memcpy(void *dst, const void *src, size_t bytes, int kind) {
 static int drop_plans(fcx_engine *e) {
   if (e->plans.empty()) return FCX_OK;
   if (e->stream) HIP_TRY(hipStreamSynchronize(e->stream));
-  for (auto &kv : e->plans) {
-    (void)hipFree(kv.second.dev);
-    (void)hipFree(kv.second.host.rec);
-  }
   e->plans.clear();
   e->rec_plan = nullptr;
   return FCX_OK;
@@ -3879,40 +3863,39 @@ extern "C" int fcx_set_atmos_map(fcx_engine *e, int64_t n_atmos, const int32_t *
   if (e->committed) return fail(FCX_E_STATE, "engine already committed");
   const int64_t n = e->n[0];
   if (n_atmos < 0 || (n > 0 && (!idx || !w))) return fail(FCX_E_ARG, "bad atmosphere map");
-  std::vector<int32_t> count((size_t)n_atmos + 1, 0);
   bool sorted = true;
   for (int64_t x = 0; x < n; ++x) {
     if (idx[x] < 0 || idx[x] >= n_atmos)
       return fail(FCX_E_ARG, "atmosphere index %d of exchange cell %lld outside 0..%lld", idx[x],
                   (long long)x, (long long)n_atmos - 1);
     if (x > 0 && idx[x] < idx[x - 1]) sorted = false;
-    count[(size_t)idx[x] + 1]++;
   }
   e->n_atmos = n_atmos;
   e->atm_idx.assign(idx, idx + n);
+  // CSR by atmosphere cell, links kept in increasing exchange cell order (sorted: cell x is link x)
+  e->atm.build(n_atmos, n, nullptr, idx, w, 0);
+  e->atm_contiguous = sorted;
+  if (sorted) e->atm.col.clear();
   e->atm_maxseg = 0;
   e->atm_empty.clear();
   for (int64_t a = 0; a < n_atmos; ++a) {
-    e->atm_maxseg = std::max(e->atm_maxseg, count[(size_t)a + 1]);
-    if (count[(size_t)a + 1] == 0) e->atm_empty.push_back((int32_t)a);
-  }
-  e->atm_row.assign((size_t)n_atmos + 1, 0);
-  for (int64_t a = 0; a < n_atmos; ++a) e->atm_row[(size_t)a + 1] = e->atm_row[(size_t)a] + count[(size_t)a + 1];
-  e->atm_contiguous = sorted;
-  e->atm_w.assign((size_t)n, 0.0);
-  e->atm_col.clear();
-  if (sorted) {
-    for (int64_t x = 0; x < n; ++x) e->atm_w[(size_t)x] = w[x];
-  } else {  // CSR by atmosphere cell, links kept in increasing exchange cell order
-    e->atm_col.assign((size_t)n, 0);
-    std::vector<int32_t> fill(e->atm_row.begin(), e->atm_row.end() - 1);
-    for (int64_t x = 0; x < n; ++x) {
-      const int32_t at = fill[(size_t)idx[x]]++;
-      e->atm_col[(size_t)at] = (int32_t)x;
-      e->atm_w[(size_t)at] = w[x];
-    }
+    const int32_t cells = e->atm.row[(size_t)a + 1] - e->atm.row[(size_t)a];
+    e->atm_maxseg = std::max(e->atm_maxseg, cells);
+    if (cells == 0) e->atm_empty.push_back((int32_t)a);
   }
   return FCX_OK;
+}
+
+// an output registered on caller memory: a host array, or device memory (FCX_MEM_DEVICE)
+static OutField out_field(int phase, int s, int g, int var, double *out, int flags) {
+  OutField f{phase, s, g, var, {}};
+  if (flags & FCX_MEM_DEVICE) {
+    f.m.dev = out;
+    f.m.external = true;
+  } else {
+    f.m.host = out;
+  }
+  return f;
 }
 
 extern "C" int fcx_add_atmos_field(fcx_engine *e, int phase, int s, int g, int var, double *out, int flags) {
@@ -3924,18 +3907,7 @@ extern "C" int fcx_add_atmos_field(fcx_engine *e, int phase, int s, int g, int v
   if (e->n[g - 1] != e->n[0]) return fail(FCX_E_UNSUPPORTED, "atmosphere fields must live on the t grid cells");
   if ((int)e->atm_fields.size() >= kMaxAtmosFields)
     return fail(FCX_E_UNSUPPORTED, "more than %d atmosphere fields", kMaxAtmosFields);
-  fcx_engine::AtmosField f;
-  f.phase = phase;
-  f.s = s;
-  f.g = g;
-  f.var = var;
-  if (flags & FCX_MEM_DEVICE) {
-    f.out_dev = out;
-    f.external = true;
-  } else {
-    f.out_host = out;
-  }
-  e->atm_fields.push_back(f);
+  e->atm_fields.push_back(out_field(phase, s, g, var, out, flags));
   return FCX_OK;
 }
 
@@ -4006,22 +3978,12 @@ extern "C" int fcx_add_remap(fcx_engine *e, int64_t n_dst, int64_t n_links, cons
   fcx_engine::Remap rm;
   rm.n_dst = n_dst;
   rm.n_links = n_links;
-  rm.row.assign((size_t)n_dst + 1, 0);
   for (int64_t k = 0; k < n_links; ++k) {
     if (dst[k] < 0 || dst[k] >= n_dst || src[k] < 0)
       return fail(FCX_E_ARG, "remap link %lld (%d -> %d) outside the grids", (long long)k, src[k], dst[k]);
-    rm.row[(size_t)dst[k] + 1]++;
     rm.max_src = std::max(rm.max_src, src[k]);
   }
-  for (int64_t d = 0; d < n_dst; ++d) rm.row[(size_t)d + 1] += rm.row[(size_t)d];
-  rm.col.assign((size_t)n_links, 0);
-  rm.w.assign((size_t)n_links, 0.0);
-  std::vector<int32_t> fill(rm.row.begin(), rm.row.end() - 1);
-  for (int64_t k = 0; k < n_links; ++k) {  // stable: each destination keeps its link order
-    const int32_t at = fill[(size_t)dst[k]]++;
-    rm.col[(size_t)at] = src[k];
-    rm.w[(size_t)at] = w[k];
-  }
+  rm.map.build(n_dst, n_links, src, dst, w, 0);
   *remap_id = (int32_t)e->remaps.size();
   e->remaps.push_back(std::move(rm));
   return FCX_OK;
@@ -4034,18 +3996,7 @@ extern "C" int fcx_add_remap_field(fcx_engine *e, int32_t remap_id, int phase, i
   if (remap_id < 0 || remap_id >= (int32_t)e->remaps.size()) return fail(FCX_E_ARG, "remap %d unknown", remap_id);
   if (phase < 1 || phase > 3 || s < 0 || s > kMaxTypes || g < 1 || g > 3 || var < 1 || var > kNumVars || !out)
     return fail(FCX_E_ARG, "bad remap field arguments");
-  fcx_engine::RemapField f;
-  f.phase = phase;
-  f.s = s;
-  f.g = g;
-  f.var = var;
-  if (flags & FCX_MEM_DEVICE) {
-    f.out_dev = out;
-    f.external = true;
-  } else {
-    f.out_host = out;
-  }
-  e->remaps[(size_t)remap_id].fields.push_back(f);
+  e->remaps[(size_t)remap_id].fields.push_back(out_field(phase, s, g, var, out, flags));
   return FCX_OK;
 }
 

@@ -356,6 +356,66 @@ def test_staging_arena_failure_falls_back_to_direct_copies(monkeypatch):
     eng.close()
 
 
+def test_heap_outputs_staged_unpinned_and_mapped(monkeypatch):
+    """Atmosphere and remap outputs on caller heap arrays, beside the fields, through the three
+    transports of heap memory: the staging arena moved by DMA (zero_copy 0), the direct copies
+    it falls back to when no image can be page-locked (FCX_TEST_PIN_FAIL=1), and the mapped
+    arena the kernels use in place (zero_copy 1).  4,099 exchange cells (one past a layout
+    tile), atmosphere runs of 3..5 cells, the six fluxes to the atmosphere and two fields to a
+    700-cell model grid; the sequential step and the chunk pipeline.  Every output has the
+    same bits every way, the fields are within tests/parity.py of the oracle, and the sums
+    are the sequential ones of the engine's own fluxes."""
+    from fcx.parallel import synthetic_model_map
+    from fcx.workload import ATM_FIELDS
+    from test_gpu_multirank import random_run_map
+
+    n = 4_099
+    case = build_case("CCLM", n=n, T=1, bias=True)
+    amap = random_run_map(n, (3, 5), seed=5)
+    mmap = synthetic_model_map(n, 700, links_per_cell=2)
+    rm_fields = (("MEVA", 1), ("UMOM", 2))
+
+    def step(options):
+        for k in case.outputs:
+            case.lf.field[k][:] = np.nan
+        atm = {name: np.full(amap.n_atmos, np.nan) for name, _ in ATM_FIELDS}
+        rmo = {name: np.full(mmap.n_model, np.nan) for name, _ in rm_fields}
+        spec = {"n_dst": mmap.n_model, "src": mmap.src, "dst": mmap.dst, "w": mmap.weight,
+                "fields": [(2, 1, g, name, rmo[name]) for name, g in rm_fields]}
+        eng = Engine(case.lf, 1, case.methods, corrections=case.corrections,
+                     atmos={"local": local_atmos(amap, 0, 1),
+                            "fields": [(2, 1, g, name, atm[name]) for name, g in ATM_FIELDS]},
+                     remaps=[spec], options=options)
+        pinned = eng.staging_bytes()
+        eng.step(PHASE_ALL, STEP_T)
+        got = {k: np.array(case.lf.field[k], copy=True) for k in case.outputs}
+        eng.close()
+        got.update({("atm", name): v for name, v in atm.items()})
+        got.update({("remap", name): v for name, v in rmo.items()})
+        return got, pinned
+
+    want = None
+    for shape in ({}, {"pipeline_min_chunk": 1024, "pipeline_chunks": 2}):
+        staged, pinned = step({"zero_copy": 0, **shape})
+        assert pinned > 0
+        monkeypatch.setenv("FCX_TEST_PIN_FAIL", "1")
+        unpinned, pinned = step({"zero_copy": 0, **shape})
+        monkeypatch.delenv("FCX_TEST_PIN_FAIL")
+        assert pinned == 0
+        mapped, _ = step({"zero_copy": 1, **shape})
+        want = want or staged
+        for got in (staged, unpinned, mapped):
+            same_bits(got, want)
+    ref = oracle_lib.run_case(case, "c", current_step_time=STEP_T)
+    assert_parity({k: want[k] for k in case.outputs}, ref, label="heap outputs")
+    for name, g in ATM_FIELDS:
+        seq = oracle_lib.atmos_accumulate(amap.atmos_index, amap.weight, want[(1, g, name)], amap.n_atmos)
+        np.testing.assert_array_equal(want[("atm", name)], seq, err_msg=name)
+    for name, g in rm_fields:
+        seq = oracle_lib.remap_apply(mmap.src, mmap.dst, mmap.weight, want[(1, g, name)], mmap.n_model)
+        np.testing.assert_array_equal(want[("remap", name)], seq, err_msg=name)
+
+
 @pytest.mark.parametrize("n", [32_768, 600_001])
 def test_step_async_engines_started_from_one_thread(n):
     """fcx_step_async (the asynchronous phase, Fortran fcx_start_phase / fcx_finish_phase):
