@@ -118,8 +118,10 @@ struct HostMirror {
   int64_t n = 0;
   bool external = false;   // caller-owned device memory (or a host array used in place)
   StageRef st;
-  // some transport moves it between host and device (not device-bound, not used in place)
-  bool moves_over_link() const { return !external || st.sp >= 0; }
+  // some transport moves it between host and device: it has a caller array at all (a constant
+  // and an output kept on the device, fcx_set_output_use, have none) that is neither device-bound
+  // nor used in place
+  bool moves_over_link() const { return host && (!external || st.sp >= 0); }
 };
 
 // bytes of a mirror of n elements of es bytes: an empty array still has one element's worth,
@@ -130,6 +132,15 @@ struct Buffer : HostMirror {
   bool in_place = false;   // a host array the kernels use through its mapped address
   int span = -1;           // fcx_host_malloc array moved by the span transport: its Span
   bool moves_over_link() const { return HostMirror::moves_over_link() || span >= 0; }
+  // fcx_set_output_use (settled at fcx_commit from the slots' declarations): FCX_OUT_DEVICE /
+  // FCX_OUT_UNREAD = a computed output in a device array of the engine's own.  The buffer has let
+  // go of the caller's array (host == nullptr, like a constant), so no transport ever sees it.
+  int8_t use = FCX_OUT_HOST;
+  // FCX_OUT_UNREAD only.  keep: something outside the whole-phase launch reads the array, so it
+  // is stored by every launch (FCX_OUT_DEVICE for good; decided at fcx_commit).  skipped: the
+  // last whole-phase plan built for it left its store out (fcx_output_info 2).  stale: the last
+  // launch that computed it left its store out -- the array does not hold the step's values.
+  bool keep = false, skipped = false, stale = false;
   // fcx_bind_constant: a namelist-constant input.  No caller array (host stays nullptr and the
   // buffer is never external), so no transport ever sees it; its mirror in the engine's pools
   // is filled with cval once at fcx_commit and only ever read.
@@ -225,7 +236,12 @@ struct Plan {
   DevArray<double> rec;  // owner of host.rec
   std::vector<int> reads, writes;  // buffer ids
   std::vector<int> const_reads;    // constant buffers the launch streams (never transferred)
-  int variant = 0;                 // T=1 specialisation (LaunchConfig::variant)
+  // FCX_OUT_UNREAD outputs the launch computes without storing (null store pointers; not in
+  // `writes`): stale after it.  needs_halo: some of them are fields of the fused accumulation,
+  // which only a launch without crossing records leaves unread (plan_unread_outputs)
+  std::vector<int> skipped;
+  bool skip_needs_halo = false;
+  int variant = 0;                // T=1 specialisation (LaunchConfig::variant)
   bool atm_fused = false;          // exchange -> atmosphere accumulation inside the launch
   AtmosFused af{};
   int atm_nf = 0;
@@ -294,6 +310,10 @@ struct fcx_engine {
   int slot[kMaxTypes + 1][3][kNumVars];
   bool allocated[kMaxTypes + 1][3][kNumVars] = {};
   uint8_t put_to[kMaxTypes + 1][3][kNumVars] = {};
+  // fcx_set_output_use per slot as declared (fcx_output_use); the buffers take them at
+  // fcx_plan_check / fcx_commit (settle_output_use)
+  int8_t out_use[kMaxTypes + 1][3][kNumVars] = {};
+  bool any_out_use = false;
   std::vector<Buffer> bufs;
   std::map<const double *, int> by_ptr;
   bool committed = false;
@@ -410,6 +430,7 @@ struct fcx_engine {
   hipEvent_t ev_stage_in = nullptr;     // the last H2D out of the arena
   bool stage_in_live = false;
   size_t pool_bytes = 0, tiled_bytes = 0, atm_pool_bytes = 0;  // device pool sizes
+  size_t pool_staged_bytes = 0;  // the leading part of `pool` that holds mirrors of host arrays
   // tile-blocked mirrors (FCX_OPT_TILED_LAYOUT): tpad = tile stride - kLayoutTile elements,
   // 0 when the field buffers are plain contiguous arrays
   bool tiled_opt = true;
@@ -689,6 +710,56 @@ extern "C" int fcx_constant_info(const fcx_engine *e, int s, int g, int var, int
   const int b = e->buf(s, g, var);
   *kind = 0;
   if (b >= 0 && e->bufs[(size_t)b].constant) *kind = e->bufs[(size_t)b].uniform && !e->bufs[(size_t)b].filled ? 1 : 2;
+  return FCX_OK;
+}
+
+static const char *grid_name(int g) { return g == 1 ? "t" : g == 2 ? "u" : "v"; }
+
+extern "C" int fcx_set_output_use(fcx_engine *e, int s, int g, int var, int use) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (e->committed) return fail(FCX_E_STATE, "engine already committed");
+  if (s < 0 || s > kMaxTypes || g < 1 || g > 3 || var < 1 || var > kNumVars)
+    return fail(FCX_E_ARG, "slot (%d,%d,%d) out of range", s, g, var);
+  if (use < FCX_OUT_HOST || use > FCX_OUT_UNREAD)
+    return fail(FCX_E_ARG, "%s(%d,%s): output use %d outside 0..2", kVarNames[var0(var)], s, grid_name(g), use);
+  e->out_use[s][g - 1][var0(var)] = (int8_t)use;
+  e->any_out_use = false;
+  for (auto &a : e->out_use)
+    for (auto &b : a)
+      for (int8_t c : b) e->any_out_use = e->any_out_use || c != FCX_OUT_HOST;
+  return FCX_OK;
+}
+
+extern "C" int fcx_output_info(const fcx_engine *e, int s, int g, int var, int32_t *kind) {
+  if (!e || !kind) return fail(FCX_E_ARG, "NULL argument");
+  if (!e->committed) return fail(FCX_E_STATE, "fcx_commit has not been called");
+  if (s < 0 || s > kMaxTypes || g < 1 || g > 3 || var < 1 || var > kNumVars)
+    return fail(FCX_E_ARG, "slot (%d,%d,%d) out of range", s, g, var);
+  const int b = e->buf(s, g, var);
+  *kind = 0;
+  if (b >= 0 && e->bufs[(size_t)b].use != FCX_OUT_HOST) *kind = e->bufs[(size_t)b].skipped ? 2 : 1;
+  return FCX_OK;
+}
+
+// The slots' declarations -> their buffers (every slot bound to the address follows; where they
+// differ, the array is kept: FCX_OUT_DEVICE).  An unbound or constant declared slot is an error.
+static int settle_output_use(fcx_engine *e) {
+  for (auto &bf : e->bufs) bf.use = FCX_OUT_HOST;
+  if (!e->any_out_use) return FCX_OK;
+  for (int s = 0; s <= kMaxTypes; ++s)
+    for (int g = 1; g <= 3; ++g)
+      for (int v = 1; v <= kNumVars; ++v) {
+        const int use = e->out_use[s][g - 1][v - 1];
+        if (use == FCX_OUT_HOST) continue;
+        const int b = e->buf(s, g, v);
+        if (b < 0)
+          return fail(FCX_E_STATE, "output use of %s(%d,%s): the slot is not bound", kVarNames[v - 1], s, grid_name(g));
+        Buffer &bf = e->bufs[(size_t)b];
+        if (bf.constant)
+          return fail(FCX_E_STATE, "output use of the constant field %s(%d,%s): a namelist constant is an input",
+                      kVarNames[v - 1], s, grid_name(g));
+        bf.use = (int8_t)(bf.use == FCX_OUT_HOST ? use : std::min<int>(bf.use, use));
+      }
   return FCX_OK;
 }
 
@@ -1102,7 +1173,9 @@ static int plan_audit(const fcx_engine *e, const Params &P0) {
     const TypeParams &tp = P.type[s];
     const TGridPtrs &t = tp.t;
     const bool q_t = (st & S_QSUR_T) && tp.m_qsur[0] == FCX_CCLM;
-    if ((st & S_RBBR) && t.rbbr && tp.m_rbbr == FCX_STBO) AUD(t.tsur, "RBBR", "TSUR");
+    // (an output wanted though not stored -- TypeParams::want -- is computed like a stored one)
+    const uint32_t w = tp.want;
+    if ((st & S_RBBR) && (t.rbbr || (w & W_RBBR)) && tp.m_rbbr == FCX_STBO) AUD(t.tsur, "RBBR", "TSUR");
     if (q_t) {
       AUD(t.fice, "QSUR(t)", "FICE");
       AUD(t.psur, "QSUR(t)", "PSUR");
@@ -1124,10 +1197,10 @@ static int plan_audit(const fcx_engine *e, const Params &P0) {
         AUD(t.vatm, "MEVA", "VATM");
       }
     }
-    if ((st & S_HLAT) && t.hlat && (tp.m_hlat == FCX_WATER || tp.m_hlat == FCX_ICE) &&
+    if ((st & S_HLAT) && (t.hlat || (w & W_HLAT)) && (tp.m_hlat == FCX_WATER || tp.m_hlat == FCX_ICE) &&
         !((st & S_MEVA) && is_compute(tp.m_meva)))
       AUD(t.meva_in, "HLAT", "MEVA");
-    if ((st & S_HSEN) && t.hsen) {
+    if ((st & S_HSEN) && (t.hsen || (w & W_HSEN))) {
       if (cclm_like(tp.m_hsen)) {
         AUD(tp.m_hsen == FCX_CCLM ? t.amoi : t.chea, "HSEN", tp.m_hsen == FCX_CCLM ? "AMOI" : "CHEA");
         for (auto pn : {std::make_pair((const void *)t.patm, "PATM"), std::make_pair((const void *)t.psur, "PSUR"),
@@ -1146,13 +1219,14 @@ static int plan_audit(const fcx_engine *e, const Params &P0) {
     if (P.merged_uv) {
       bool q_uv = false;
       for (int k = 0; k < 2; ++k)
-        if ((st & (k == 0 ? S_QSUR_U : S_QSUR_V)) && tp.m_qsur[1 + k] == FCX_CCLM && tp.uv[k].qsur) {
+        if ((st & (k == 0 ? S_QSUR_U : S_QSUR_V)) && tp.m_qsur[1 + k] == FCX_CCLM &&
+            (tp.uv[k].qsur || (w & (k == 0 ? W_QSUR_U : W_QSUR_V)))) {
           q_uv = true;
           AUD(t.fice, k ? "QSUR(v)" : "QSUR(u)", "FICE");
           AUD(t.psur, k ? "QSUR(v)" : "QSUR(u)", "PSUR");
           AUD(t.tsur, k ? "QSUR(v)" : "QSUR(u)", "TSUR");
         }
-      const bool mom = ((st & S_UMOM) && tp.uv[0].mom) || ((st & S_VMOM) && tp.uv[1].mom);
+      const bool mom = ((st & S_UMOM) && (tp.uv[0].mom || (w & W_UMOM))) || ((st & S_VMOM) && (tp.uv[1].mom || (w & W_VMOM)));
       if (mom && cclm_like(tp.m_mom)) {
         AUD(tp.m_mom == FCX_CCLM ? tp.uv[0].amom : tp.uv[0].cmom, "UMOM/VMOM", tp.m_mom == FCX_CCLM ? "AMOM" : "CMOM");
         AUD(t.psur, "UMOM/VMOM", "PSUR");
@@ -1169,7 +1243,8 @@ static int plan_audit(const fcx_engine *e, const Params &P0) {
         if (P.n[1 + k] <= 0) continue;
         const UVGridPtrs &g = tp.uv[k];
         const char *wq = k ? "QSUR(v)" : "QSUR(u)", *wm = k ? "VMOM" : "UMOM";
-        const bool do_q = (st & (k == 0 ? S_QSUR_U : S_QSUR_V)) && tp.m_qsur[1 + k] == FCX_CCLM && g.qsur;
+        const bool do_q = (st & (k == 0 ? S_QSUR_U : S_QSUR_V)) && tp.m_qsur[1 + k] == FCX_CCLM &&
+                          (g.qsur || (w & (k == 0 ? W_QSUR_U : W_QSUR_V)));
         const bool do_m = (st & (k == 0 ? S_UMOM : S_VMOM)) && g.mom;
         if (do_q) {
           AUD(g.fice, wq, "FICE");
@@ -1203,6 +1278,106 @@ static int plan_audit(const fcx_engine *e, const Params &P0) {
 #undef AUD
   (void)e;
   return FCX_OK;
+}
+
+static int full_range_halo(const fcx_engine *e, const Plan *pl);
+static uint32_t phase_stages(int phase);
+
+// FCX_OUT_UNREAD outputs of a whole-phase plan (fcx_set_output_use): the store pointer of every
+// one whose only consumer is the launch's own registers becomes null, its buffer moves from the
+// plan's writes to `skipped`, and where a later flux block, a register average or the fused
+// accumulation consumes the value its TypeParams::want bit is set, so the block still runs.  An
+// output stays stored (FCX_OUT_DEVICE behaviour) when
+//  - the buffer is kept for good (Buffer::keep, decide_output_keep), or is a type-0 output;
+//  - the launch itself reads the array: as qsur_in / meva_in, or an average that re-reads x[s];
+//  - it is accumulated to the atmosphere outside the launch's registers: by atmos_kernel (the
+//    accumulation is not fused, or belongs to another phase) or by the crossing-record fix-up
+//    (a launch without halo tiles on a map with crossings; pipelined chunk launches are such);
+//  - a consumer in the launch needs a want bit and the kernel family does not take the
+//    unstored path (skip_family: the same rule the kernels are compiled with).
+// Per-call subroutine plans, the stages of the regrid sequence and explicit averages never skip.
+static void plan_unread_outputs(fcx_engine *e, Plan &pl, uint32_t stages, int phase) {
+  pl.skipped.clear();
+  pl.skip_needs_halo = false;
+  if (!e->any_out_use) return;
+  Params &P = pl.host;
+  const bool whole = phase >= 1 && phase <= 3 && stages == phase_stages(phase) && !e->any_regrid;
+  // the launches this plan can take (plan_launch): the variant, fused or not, halo tiles or not
+  const int variant = (e->specialize && P.merged_uv) ? pl.variant : 0;
+  const bool fused = pl.atm_fused && variant && e->launch.cells_per_thread == 2 && e->aligned16;
+  const bool halo = fused && full_range_halo(e, &pl) > 0;
+  bool link = false;  // some array of the plan moves over the host link: the step may be pipelined
+  for (const std::vector<int> *ids : {&pl.reads, &pl.writes})
+    for (int b : *ids) link = link || e->bufs[(size_t)b].moves_over_link();
+  const bool chunked = link && e->chunks > 1 && P.n_max >= 2 * e->min_chunk;  // (fcx_step's rule)
+  const bool tm1 = P.num_types == 1, ravg = P.ravg_on != 0, merged = P.merged_uv != 0;
+  const bool want_ok = skip_family(e->f32, variant, ravg, tm1, merged, halo) &&
+                       (!(chunked || !halo) || skip_family(e->f32, variant, ravg, tm1, merged, false));
+  // the crossing-record fix-up reads the accumulated fields' arrays
+  const bool fixup_reads = fused && e->atm_crossings > 0 && (!halo || chunked);
+  std::set<const double *> read_here;
+  for (int s = 0; s < P.num_types; ++s) {
+    const TypeParams &tp = P.type[s];
+    read_here.insert(tp.t.qsur_in);
+    read_here.insert(tp.t.meva_in);
+    for (int k = 0; k < 2; ++k) read_here.insert(tp.uv[k].qsur_in);
+  }
+  for (int a = 0; a < P.num_avg; ++a)
+    for (int s = 0; s < P.num_types; ++s) read_here.insert(P.avg[a].x[s]);
+  std::set<int> skipped;
+  // slot: the value's register slot (AvgSlot / AtmosFused order), -1 = none; wbit: its want bit
+  auto consider = [&](double *&ptr, int s, int g, int var, int slot, uint32_t wbit, uint8_t &want) {
+    const int b = e->buf(s, g, var);
+    if (!ptr || b < 0) return;
+    Buffer &bf = e->bufs[(size_t)b];
+    if (bf.use != FCX_OUT_UNREAD) return;
+    // (fcx_output_info 2 speaks of the last WHOLE-PHASE plan built: a per-call subroutine's plan,
+    // which always stores, leaves the answer alone; dry plans never come here)
+    if (!whole) return;
+    bf.skipped = false;
+    if (bf.keep || read_here.count(ptr)) return;
+    bool needs_halo = false;
+    for (const auto &f : e->atm_fields) {
+      if (e->buf(f.s, f.g, f.var) != b) continue;
+      if (!fused || !(f.phase & phase) || slot < 0 || pl.af.x[slot] != ptr || fixup_reads) return;
+      needs_halo = needs_halo || e->atm_crossings > 0;
+    }
+    const bool consumed = slot >= 0 && ((ravg && P.ravg.out[slot]) || (fused && tm1 && pl.af.out[slot]));
+    if (consumed && wbit && !want_ok) return;
+    if (consumed) want |= (uint8_t)wbit;
+    ptr = nullptr;
+    bf.skipped = true;
+    skipped.insert(b);
+    pl.skip_needs_halo = pl.skip_needs_halo || needs_halo;
+  };
+  for (int s = 1; s <= P.num_types; ++s) {
+    TypeParams &tp = P.type[s - 1];
+    consider(tp.t.rbbr, s, 1, FCX_RBBR, A_RBBR, W_RBBR, tp.want);
+    consider(tp.t.hlat, s, 1, FCX_HLAT, A_HLAT, W_HLAT, tp.want);
+    consider(tp.t.hsen, s, 1, FCX_HSEN, A_HSEN, W_HSEN, tp.want);
+    const bool cclm_mom = tp.m_mom == FCX_CCLM || tp.m_mom == FCX_MOM5;
+    for (int k = 0; k < 2; ++k) {
+      // (separate u / v grids: nothing in the launch consumes a momentum but its store)
+      consider(tp.uv[k].mom, s, 2 + k, k ? FCX_VMOM : FCX_UMOM, merged ? (k ? A_VMOM : A_UMOM) : -1,
+               k ? W_VMOM : W_UMOM, tp.want);
+      // QSUR(u / v) feeds the grid's momentum: wanted where that is still computed
+      const bool mom_runs = cclm_mom && (tp.uv[k].mom || (tp.want & (k ? W_VMOM : W_UMOM)));
+      if (!tp.uv[k].qsur || (mom_runs && !want_ok)) continue;
+      uint8_t none = 0;
+      consider(tp.uv[k].qsur, s, 2 + k, FCX_QSUR, -1, 0, none);
+      if (!tp.uv[k].qsur && mom_runs) tp.want |= (uint8_t)(k ? W_QSUR_V : W_QSUR_U);
+    }
+    // QSUR(t) and MEVA: their blocks compute whatever the pointer says (no want bit)
+    uint8_t none = 0;
+    consider(tp.t.qsur, s, 1, FCX_QSUR, -1, 0, none);
+    consider(tp.t.meva, s, 1, FCX_MEVA, A_MEVA, 0, none);
+  }
+  if (skipped.empty()) return;
+  pl.skipped.assign(skipped.begin(), skipped.end());
+  std::vector<int> kept;
+  for (int b : pl.writes)
+    if (!skipped.count(b)) kept.push_back(b);
+  pl.writes.swap(kept);
 }
 
 static int build_plan(fcx_engine *e, uint32_t stages, int avg_phases, Plan &pl) {
@@ -1483,6 +1658,9 @@ static int build_plan(fcx_engine *e, uint32_t stages, int avg_phases, Plan &pl) 
     if (int r = fill_constant(e, e->bufs[(size_t)b])) return r;
   plan_fused_atmos(e, pl, stages, avg_phases);
   if (int r = plan_fused_records(e, pl, stages, avg_phases)) return r;
+  plan_unread_outputs(e, pl, stages, avg_phases);
+  if (!pl.skipped.empty())  // the audit accepts a null output a consumer in the launch wants
+    if (int r = plan_audit(e, P)) return r;
   HIP_TRY(pl.dev.alloc(sizeof(Params)));
   HIP_TRY(hipMemcpy(pl.dev, &P, sizeof(Params), hipMemcpyHostToDevice));
   return FCX_OK;
@@ -1553,6 +1731,7 @@ extern "C" int fcx_plan_check(fcx_engine *e) {
   if (!e) return fail(FCX_E_ARG, "NULL engine");
   if (e->committed) return fail(FCX_E_STATE, "fcx_plan_check runs before fcx_commit");
   if (int r = validate(e)) return r;
+  if (int r = settle_output_use(e)) return r;
   decide_uniform(e);
   return plan_check_all(e);
 }
@@ -1574,17 +1753,74 @@ static int plan_check_all(fcx_engine *e, bool constants_only) {
   for (auto &a : e->averages) sets.push_back({S_AVG, 1000 + 100 * a.second.first + a.second.second});
   e->plan_dry = true;
   int rc = FCX_OK;
+  std::vector<char> written(e->bufs.size(), 0);  // per buffer: some plan stores it
   for (auto &x : sets) {
     Plan p;
     const std::string saved = g_err;
     e->const_error = false;
-    if ((rc = build_plan(e, x.first, x.second, p)) == FCX_OK) continue;
+    if ((rc = build_plan(e, x.first, x.second, p)) == FCX_OK) {
+      for (int b : p.writes) written[(size_t)b] = 1;
+      continue;
+    }
     if (!constants_only || e->const_error) break;
     rc = FCX_OK;
     g_err = saved;
   }
   e->plan_dry = false;
-  return rc;
+  if (rc || !e->any_out_use) return rc;
+  // fcx_set_output_use declares what the host does with an OUTPUT: a declared slot no plan
+  // writes (an input, a flux with method 'none') is an error.  Regrid destinations are written
+  // by do_regridding.
+  for (int s = 0; s <= kMaxTypes; ++s)
+    for (int g = 1; g <= 3; ++g)
+      for (int v = 1; v <= kNumVars; ++v)
+        for (int k = 0; k < 3; ++k)
+          if (((e->put_to[s][g - 1][v - 1] >> k) & 1) && k + 1 != g && e->buf(s, k + 1, v) >= 0)
+            written[(size_t)e->buf(s, k + 1, v)] = 1;
+  for (int s = 0; s <= kMaxTypes; ++s)
+    for (int g = 1; g <= 3; ++g)
+      for (int v = 1; v <= kNumVars; ++v)
+        if (e->out_use[s][g - 1][v - 1] != FCX_OUT_HOST && !written[(size_t)e->buf(s, g, v)])
+          return fail(FCX_E_STATE, "output use of %s(%d,%s): no plan writes the slot (it is not a computed output)",
+                      kVarNames[v - 1], s, grid_name(g));
+  return FCX_OK;
+}
+
+// Which FCX_OUT_UNREAD buffers stay FCX_OUT_DEVICE for good (Buffer::keep): those something
+// outside a whole-phase launch reads.  Any regridding of the engine (its phases run as the staged
+// sequence, whose stages read each other's arrays), a remap (its source, also where the flux
+// launch writes its packed records), a 'copy' consumer, and a whole phase that reads the array
+// without producing it (qsur_in / meva_in, an average's field).  What depends on the launch --
+// the separate accumulation, the crossing-record fix-up, an average that re-reads a field the
+// launch produced -- is decided per plan (plan_unread_outputs).
+static void decide_output_keep(fcx_engine *e) {
+  if (!e->any_out_use) return;
+  auto keep = [&](int s, int g, int v) {
+    const int b = e->buf(s, g, v);
+    if (b >= 0) e->bufs[(size_t)b].keep = true;
+  };
+  for (auto &bf : e->bufs) bf.keep = e->any_regrid;
+  for (auto &rm : e->remaps)
+    for (auto &f : rm.fields) keep(f.s, f.g, f.var);
+  static const struct {
+    int flux, g, var;
+  } kCopy[] = {{FCX_SPEC_VAPOR_SURFACE_T, 1, FCX_QSUR}, {FCX_SPEC_VAPOR_SURFACE_T + 1, 2, FCX_QSUR},
+               {FCX_SPEC_VAPOR_SURFACE_T + 2, 3, FCX_QSUR}, {FCX_FLUX_MASS_EVAP, 1, FCX_MEVA},
+               {FCX_FLUX_HEAT_LATENT, 1, FCX_HLAT}, {FCX_FLUX_HEAT_SENSIBLE, 1, FCX_HSEN},
+               {FCX_FLUX_MOMENTUM, 2, FCX_UMOM}, {FCX_FLUX_MOMENTUM, 3, FCX_VMOM},
+               {FCX_FLUX_RADIATION_BLACKBODY, 1, FCX_RBBR}};
+  for (int s = 2; s <= e->T; ++s)
+    for (auto &c : kCopy)
+      if (e->method[c.flux][s - 1] == FCX_COPY) keep(1, c.g, c.var), keep(s, c.g, c.var);
+  const std::string saved = g_err;
+  e->plan_dry = true;
+  for (int ph = 1; ph <= 3 && !e->any_regrid; ++ph) {
+    Plan p;
+    if (build_plan(e, phase_stages(ph), ph, p) != FCX_OK) continue;
+    for (int b : p.reads) e->bufs[(size_t)b].keep = true;  // read, not produced there
+  }
+  e->plan_dry = false;
+  g_err = saved;
 }
 
 static int get_plan(fcx_engine *e, uint32_t stages, int avg_phases, Plan **pl) {
@@ -1939,10 +2175,12 @@ static int alloc_tiled(fcx_engine *e) {
   // pool and slot of every buffer: read pool, write pool, then the cold ones S to a pool
   std::vector<std::pair<int, int>> at(e->bufs.size());
   int npools = 0, fill[3] = {0, 0, 0}, pool_of[2] = {-1, -1}, cold_pool = -1;
-  std::vector<size_t> order;  // the constants after the arrays
+  // the constants, and the outputs kept on the device (fcx_set_output_use), after the arrays
+  // that move over the link, which so stay one run of slots
+  std::vector<size_t> order;
   for (int pass = 0; pass < 2; ++pass)
     for (size_t b = 0; b < e->bufs.size(); ++b)
-      if (e->bufs[b].constant == (pass == 1)) order.push_back(b);
+      if ((e->bufs[b].constant || e->bufs[b].use != FCX_OUT_HOST) == (pass == 1)) order.push_back(b);
   for (size_t b : order) {
     const int c = cls[b];
     if (c != kCold) {
@@ -2055,7 +2293,7 @@ static void stage_setup(fcx_engine *e) {
   for (auto &p : e->tiled_pools)
     cand.push_back(StagePool{(char *)p.p, nullptr, e->tiled_bytes, true, (size_t)kLayoutTile * es,
                              (size_t)(kLayoutTile + e->tpad) * es});
-  if (e->pool) cand.push_back(StagePool{(char *)e->pool.p, nullptr, e->pool_bytes, false, 0, 0});
+  if (e->pool) cand.push_back(StagePool{(char *)e->pool.p, nullptr, e->pool_staged_bytes, false, 0, 0});
   int atm_cand = -1;  // records: the pool the downloads read does not exist yet (atm_unpack)
   if (e->atm_pool) {
     const bool t = e->atm_out_tpad != 0;
@@ -2412,6 +2650,19 @@ static double remap_scatter(const fcx_engine::Remap &rm) {
 
 // ---- fcx_commit, step by step (in the order fcx_commit calls them)
 
+// Outputs kept on the device (fcx_set_output_use): the buffer lets go of the caller's array
+// before any transport is chosen, so it is an engine-owned device array like a constant's --
+// never mapped, spanned, staged or used in place, and never a reason to leave the tiled pools.
+// (A slot bound as caller device memory stays where it is: it crosses no link.)
+static int commit_output_use(fcx_engine *e) {
+  for (auto &bf : e->bufs) {
+    if (bf.use == FCX_OUT_HOST || bf.external) continue;
+    e->by_ptr.erase(bf.host);
+    bf.host = nullptr;
+  }
+  return FCX_OK;
+}
+
 // which transport moves every host array: in place, a span, or (the rest) a mirror
 static int commit_transports(fcx_engine *e) {
   for_each_output(e, [&](OutField &f, MirrorOf kind, size_t k) {
@@ -2453,13 +2704,20 @@ static int commit_field_pools(fcx_engine *e) {
   // plain layout: one pooled allocation for all host-bound mirrors, 256-B aligned sub-buffers
   size_t total = 0;
   std::vector<size_t> off(e->bufs.size(), 0);
-  for (size_t b = 0; b < e->bufs.size() && e->tiled_pools.empty(); ++b) {
-    if (e->bufs[b].external) continue;
-    off[b] = total;
-    total += ((size_t)e->bufs[b].n * e->esize + 255) / 256 * 256;
+  // (the outputs kept on the device, fcx_set_output_use, behind everything else: the pool's
+  // page-locked staging image ends where they begin -- they have no place in the arena)
+  size_t staged = 0;
+  for (int pass = 0; pass < 2 && e->tiled_pools.empty(); ++pass) {
+    for (size_t b = 0; b < e->bufs.size(); ++b) {
+      if (e->bufs[b].external || (e->bufs[b].use != FCX_OUT_HOST) != (pass == 1)) continue;
+      off[b] = total;
+      total += ((size_t)e->bufs[b].n * e->esize + 255) / 256 * 256;
+    }
+    if (pass == 0) staged = total;
   }
   if (total) {
     e->pool_bytes = total;
+    e->pool_staged_bytes = staged;
     hipError_t err = e->pool.alloc(total);
     if (err != hipSuccess)
       return fail(FCX_E_NOMEM, "hipMalloc(%zu) for the field mirrors: %s", total, hipGetErrorString(err));
@@ -2678,12 +2936,15 @@ extern "C" int fcx_commit(fcx_engine *e) {
   if (!e) return fail(FCX_E_ARG, "NULL engine");
   if (e->committed) return FCX_OK;
   if (int r = validate(e)) return r;
+  if (int r = settle_output_use(e)) return r;
   decide_uniform(e);
-  // a constant some plan would write is an error here, not at that plan's first run
-  if (std::any_of(e->bufs.begin(), e->bufs.end(), [](const Buffer &bf) { return bf.constant; }))
+  // a constant some plan would write, or a declared output none writes, is an error here, not
+  // at that plan's first run
+  if (e->any_out_use || std::any_of(e->bufs.begin(), e->bufs.end(), [](const Buffer &bf) { return bf.constant; }))
     if (int r = plan_check_all(e, true)) return r;
+  decide_output_keep(e);
   if (int r = gpu_init(e)) return r;
-  for (auto step : {commit_transports, commit_field_pools, commit_constants, commit_corrections, commit_maps,
+  for (auto step : {commit_output_use, commit_transports, commit_field_pools, commit_constants, commit_corrections, commit_maps,
                     commit_atmos_outputs, commit_shared_slots, commit_remaps, commit_staging})
     if (int r = step(e)) return r;
   return FCX_OK;
@@ -2722,7 +2983,7 @@ static int copy_bufs(fcx_engine *e, const std::vector<int> &ids, bool h2d, std::
   bool direct = false;
   for (int b : ids) {
     const Buffer &bf = e->bufs[b];
-    if (bf.n == 0 || bf.constant) continue;
+    if (bf.n == 0 || !bf.moves_over_link()) continue;  // (a constant, an output kept on the device, in place)
     if (h2d && (size_t)b < e->field_sent.size() && e->field_sent[(size_t)b]) continue;  // fcx_upload_field
     if (bf.st.sp >= 0) {  // (also a heap array whose mirror is a mapped arena image)
       xs.push_back(xfer_of(bf.st, bf.host, bf.n));
@@ -2817,11 +3078,55 @@ static int launch_fixup(fcx_engine *e, Plan *pl, const LaunchConfig &lc) {
   return FCX_OK;
 }
 
+// The stale flag of the FCX_OUT_UNREAD buffers (fcx_set_output_use).  A launch that left an
+// output's store out leaves its device array stale, a launch that stored it makes it current;
+// whatever would READ a stale array fails by name before anything is launched.
+static const char *slot_name(const fcx_engine *e, int b, char *buf, size_t len) {
+  for (int s = 0; s <= kMaxTypes; ++s)
+    for (int g = 1; g <= 3; ++g)
+      for (int v = 1; v <= kNumVars; ++v)
+        if (e->slot[s][g - 1][v - 1] == b) {
+          snprintf(buf, len, "%s(%d,%s)", kVarNames[v - 1], s, g == 1 ? "t" : g == 2 ? "u" : "v");
+          return buf;
+        }
+  snprintf(buf, len, "buffer %d", b);
+  return buf;
+}
+
+static int stale_check(const fcx_engine *e, int b, const char *reader) {
+  if (b < 0 || !e->bufs[(size_t)b].stale) return FCX_OK;
+  char name[48];
+  return fail(FCX_E_STATE, "%s would read %s, whose store the last launch that computed it left out "
+                           "(FCX_OUT_UNREAD): its device array is stale", reader, slot_name(e, b, name, sizeof name));
+}
+
+static int plan_stale_check(const fcx_engine *e, const Plan *pl) {
+  if (!e->any_out_use) return FCX_OK;
+  for (int b : pl->reads)
+    if (int r = stale_check(e, b, "the launch")) return r;
+  return FCX_OK;
+}
+
+// A launch of plan pl in the shape lc is about to be queued (fcx_run's launch, a pipelined chunk,
+// a member of fcx_run_group): refused when the plan left accumulated fields unstored and this
+// launch carries crossing records, whose fix-up would read them (the options that decide the
+// shape drop the plans of an engine with unread outputs, so a plan is never launched in a shape
+// it was not built for; checked all the same, in one place for every path); then the stale flags.
+static int plan_launched(fcx_engine *e, const Plan *pl, const LaunchConfig &lc, bool fused) {
+  if (!e->any_out_use) return FCX_OK;
+  if (pl->skip_needs_halo && fused && !lc.halo && e->atm_crossings > 0)
+    return fail(FCX_E_STATE, "a launch with crossing records of a plan whose accumulated fields are not stored");
+  for (int b : pl->writes) e->bufs[(size_t)b].stale = false;
+  for (int b : pl->skipped) e->bufs[(size_t)b].stale = true;
+  return FCX_OK;
+}
+
 static int launch_plan(fcx_engine *e, Plan *pl, const double *corr_m, int64_t lo = 0, int64_t hi = -1,
                        bool fixup = true) {
   if (pl->host.n_max <= 0) return FCX_OK;
   bool fused = false;
   const LaunchConfig lc = plan_launch(e, pl, lo, hi, &fused);
+  if (int r = plan_launched(e, pl, lc, fused)) return r;
   e->rec_written = lc.rec;
   const int r = launch_cells(&pl->host, pl->dev, corr_m, lc, e->stream, fused ? &pl->af : nullptr);
   if (r) return fail(FCX_E_HIP, "cells_kernel launch: %s", hipGetErrorString((hipError_t)r));
@@ -2965,6 +3270,7 @@ extern "C" int fcx_upload_field(fcx_engine *e, int s, int g, int var) {
   const int b = e->buf(s, g, var);
   if (b < 0) return fail(FCX_E_ARG, "local_field(%d,%d)%%var(%s) is not bound", s, g, kVarNames[var - 1]);
   if (e->bufs[(size_t)b].constant) return FCX_OK;  // nothing to hand over: the engine filled it at commit
+  if (e->bufs[(size_t)b].use != FCX_OUT_HOST) return FCX_OK;  // an output kept on the device: no host array to hand over
   if (e->field_sent.size() != e->bufs.size()) e->field_sent.assign(e->bufs.size(), 0);
   if (e->field_sent[(size_t)b]) return FCX_OK;  // an alias of a field already handed over
   e->field_sent[(size_t)b] = 1;
@@ -2985,6 +3291,7 @@ extern "C" int fcx_upload(fcx_engine *e, int phase) {
   if (phase < 1 || phase > 3) return fail(FCX_E_ARG, "phase %d unknown", phase);
   Plan *pl;
   if (int r = get_plan(e, phase_stages(phase), phase, &pl)) return r;
+  if (int r = plan_stale_check(e, pl)) return r;
   return copy_bufs(e, pl->reads, true);
 }
 
@@ -3081,6 +3388,9 @@ static int run_atmos(fcx_engine *e, int phase) {
   if (e->n_atmos < 0 || e->atm_fields.empty()) return FCX_OK;
   const AtmosArgs a = atmos_args(e, phase);
   if (a.nf == 0) return FCX_OK;
+  for (const auto &f : e->atm_fields)  // (e.g. fcx_run_atmos after a fused run that stored no fluxes)
+    if (f.phase & phase)
+      if (int r = stale_check(e, e->buf(f.s, f.g, f.var), "the atmosphere accumulation")) return r;
   const int r = launch_atmos(a, e->stream);
   if (r) return fail(FCX_E_HIP, "atmos_kernel launch: %s", hipGetErrorString((hipError_t)r));
   return FCX_OK;
@@ -3194,6 +3504,7 @@ extern "C" int fcx_run(fcx_engine *e, int phase, int32_t t) {
   if (!e->any_regrid) {
     Plan *pl;
     if (int r = get_plan(e, phase_stages(phase), phase, &pl)) return r;
+    if (int r = plan_stale_check(e, pl)) return r;
     if (int r = launch_plan(e, pl, corr_m)) return r;
     e->rec_plan = e->rec_written ? pl : nullptr;  // run_remaps gathers the records it wrote
   } else {
@@ -3236,6 +3547,7 @@ static int select_group(fcx_engine *const *es, int n, int phase, int32_t t, std:
       m.corr_m = month_slice(e, t, &rc);
       if (rc) return rc;
       if (int r = get_plan(e, phase_stages(phase), phase, &m.pl)) return r;
+      if (int r = plan_stale_check(e, m.pl)) return r;
       bool fused = false;
       m.lc = plan_launch(e, m.pl, 0, -1, &fused);
       // one surface type, or several with the type-0 averages in registers (fp64, no halo)
@@ -3311,6 +3623,8 @@ static void group_members(const GroupLaunchMember *mem, int nm, GroupMember *gm)
 // and their empty-cell stores (what precedes run_tail in fcx_run)
 static int launch_group(const GroupLaunchMember *mem, int nm) {
   GroupMember gm[kMaxGroup];
+  for (int k = 0; k < nm; ++k)  // (every member's launch is a fused one: select_group)
+    if (int r = plan_launched(mem[k].e, mem[k].pl, mem[k].lc, true)) return r;
   group_members(mem, nm, gm);
   const int r = launch_cells_group(gm, nm, mem[0].lc, mem[0].e->stream);
   if (r) return fail(FCX_E_HIP, "cells_atmos_group_kernel launch: %s", hipGetErrorString((hipError_t)r));
@@ -3485,6 +3799,7 @@ extern "C" int fcx_step(fcx_engine *e, int phase, int32_t t) {
   if (e->chunks > 1 && !e->any_regrid && !handed) {  // (fields handed over: the sequential step)
     Plan *pl;
     if (int r = get_plan(e, phase_stages(phase), phase, &pl)) return r;
+    if (int r = plan_stale_check(e, pl)) return r;
     if (host_bound(e, pl) && pl->host.n_max >= 2 * e->min_chunk) return step_pipelined(e, phase, t, pl);
   }
   if (int r = fcx_upload(e, phase)) return r;
@@ -3505,6 +3820,7 @@ extern "C" int fcx_step_async(fcx_engine *e, int phase, int32_t t) {
   if (e->chunks > 1 && !e->any_regrid && !handed) {  // (fields handed over: the sequential step)
     Plan *pl;
     if (int r = get_plan(e, phase_stages(phase), phase, &pl)) return r;
+    if (int r = plan_stale_check(e, pl)) return r;
     if (host_bound(e, pl) && pl->host.n_max >= 2 * e->min_chunk) return step_pipelined(e, phase, t, pl);
   }
   if (int r = fcx_upload(e, phase)) return r;
@@ -3529,6 +3845,7 @@ static int per_call(fcx_engine *e, uint32_t stages, int avg_phases, int32_t t) {
   if (int r = check(e)) return r;
   Plan *pl;
   if (int r = get_plan(e, stages, avg_phases, &pl)) return r;
+  if (int r = plan_stale_check(e, pl)) return r;
   int rc;
   const double *corr_m = (stages & S_MEVA) ? month_slice(e, t, &rc) : nullptr;
   if ((stages & S_MEVA) && rc) return rc;
@@ -3619,6 +3936,7 @@ extern "C" int fcx_device_ptr(fcx_engine *e, int s, int g, int var, double **dpt
   if (!dptr || s < 0 || s > kMaxTypes || g < 1 || g > 3 || var < 1 || var > kNumVars)
     return fail(FCX_E_ARG, "bad arguments");
   const int b = e->buf(s, g, var);
+  if (int r = stale_check(e, b, "fcx_device_ptr")) return r;
   if (b >= 0 && e->bufs[(size_t)b].constant && !e->bufs[(size_t)b].filled && e->bufs[(size_t)b].n > 0) {
     // a uniform constant asked for as an array: its mirror is filled now (the plans keep the value)
     if (int r = fill_constant(e, e->bufs[(size_t)b])) return r;
@@ -3802,13 +4120,21 @@ extern "C" int fcx_set_option(fcx_engine *e, int option, int64_t value) {
       if (value < kChunkAlign || value % kChunkAlign)
         return fail(FCX_E_ARG, "pipeline min chunk %lld: a positive multiple of %lld cells", (long long)value,
                     (long long)kChunkAlign);
+      // (with unread outputs a plan is built for the launches it can take, halo tiles or chunks:
+      // plan_unread_outputs)
+      if (e->any_out_use && e->min_chunk != value)
+        if (int r = drop_plans(e)) return r;
       e->min_chunk = value;
       return FCX_OK;
     case FCX_OPT_PIPELINE_CHUNKS:
       if (value < 1 || value > 1024) return fail(FCX_E_ARG, "pipeline chunks %lld outside 1..1024", (long long)value);
+      if (e->any_out_use && e->chunks != (int)value)
+        if (int r = drop_plans(e)) return r;
       e->chunks = (int)value;
       return FCX_OK;
     case FCX_OPT_ATMOS_HALO:
+      if (e->any_out_use && e->atm_halo != (value != 0))
+        if (int r = drop_plans(e)) return r;
       e->atm_halo = value != 0;
       return FCX_OK;
     case FCX_OPT_HOST_STAGING:

@@ -96,7 +96,12 @@ struct TypeParams {
   UVGridPtrs uv[2];
   int8_t m_qsur[3], m_meva, m_hlat, m_hsen, m_mom, m_rbbr;
   int8_t bias_adds;  // how many times corr(month) is added to MEVA (1 + #'copy' aliases)
-  int8_t pad[3];
+  // Outputs computed though not stored (fcx_set_output_use, FCX_OUT_UNREAD): bit WantBit of a flux
+  // set = its store pointer is null, but a consumer inside the launch (a later flux, a register
+  // average, the fused accumulation, remap records) needs the value, so the block runs and only
+  // its store is left out.  The byte behind bias_adds: it arrives with the same scalar load.
+  uint8_t want;
+  int8_t pad[2];
   // Wave-uniform inputs (fcx_bind_constant): bit ConstBit of an input of t / uv[0] / uv[1] set =
   // that member's 8 bytes hold the VALUE (the double's bits; in an fp32 engine the float's bits
   // in the low word), not an address, and the flux pass issues no vector load for it.  The
@@ -108,6 +113,33 @@ enum ConstBit : int {  // TGridPtrs inputs 0..10, UVGridPtrs inputs of uv[k] at 
   kUvBit0 = 11, KU_TSUR = 0, KU_FICE, KU_PSUR, KU_UATM, KU_VATM, KU_AMOM, KU_CMOM, kUvBits = 7
 };
 static_assert(kUvBit0 + 2 * kUvBits <= 32, "TypeParams::cmask: 25 bits");
+// TypeParams::want.  QSUR(t) and MEVA need no bit: their blocks compute whatever the pointer says.
+enum WantBit : uint32_t {
+  W_RBBR = 1u << 0, W_HLAT = 1u << 1, W_HSEN = 1u << 2, W_UMOM = 1u << 3, W_VMOM = 1u << 4,
+  W_QSUR_U = 1u << 5, W_QSUR_V = 1u << 6
+};
+// the unstored-output path in the kernels (A/B builds: 0 = every computed output is stored)
+#ifndef FCX_SKIP_STORES
+#define FCX_SKIP_STORES 1
+#endif
+// Which kernel family may leave out the store of a wanted output (TypeParams::want) -- ONE rule
+// for the kernels (process: elsewhere the byte is a compile-time zero and the code is the stored
+// path's) and for the planner (build_plan: elsewhere an FCX_OUT_UNREAD output with a consumer in
+// the launch keeps a stored device array).  An output nothing in the launch consumes is a null
+// pointer without a want bit, which every family skips as it always has.  Three families do
+// not take the path (profiles/r12/): the fp64 CCLM single-type kernel with
+// halo tiles (20 B of scratch per lane with it), the fp64 generic multi-type kernel of merged
+// grids without register averages (a wave per SIMD at one cell per lane; nothing in that kernel
+// consumes a flux but its store, so it never wants one), and the register-average kernels (they
+// kept their registers, but the T = 2 bench step was slower with it in every process pair).
+// tm1: one surface type fixed at compile time; halo: a launch with halo tiles.
+constexpr bool skip_family(bool f32, int variant, bool ravg, bool tm1, bool merged, bool halo) {
+  if (!FCX_SKIP_STORES) return false;
+  if (ravg) return false;
+  if (!f32 && variant == 1 && tm1 && halo) return false;
+  if (!f32 && variant == 0 && !tm1 && !ravg && merged) return false;
+  return true;
+}
 // the wave-uniform inputs in the kernels (A/B builds: 0 = every input is an array)
 #ifndef FCX_CONST_UNIFORM
 #define FCX_CONST_UNIFORM 1
@@ -133,6 +165,8 @@ static_assert(offsetof(TypeParams, m_qsur) % 8 == 0 && offsetof(TypeParams, m_me
 static_assert(offsetof(TypeParams, bias_adds) == offsetof(TypeParams, m_qsur) + 8 &&
                   sizeof(TypeParams) == offsetof(TypeParams, bias_adds) + 8,
               "TypeParams: bias_adds and its padding are the next aligned 64-bit word");
+static_assert(offsetof(TypeParams, want) == offsetof(TypeParams, bias_adds) + 1 && sizeof(TypeParams::want) == 1,
+              "TypeParams: want is byte 1 of the bias_adds word");
 static_assert(offsetof(TypeParams, cmask) == offsetof(TypeParams, bias_adds) + 4,
               "TypeParams: cmask is the high half of the bias_adds word");
 static_assert(sizeof(TypeParams) % 8 == 0 && alignof(TypeParams) == 8, "TypeParams: 8-B aligned in Params::type[]");

@@ -144,6 +144,7 @@ struct Methods {
   int8_t qsur[3], meva, hlat, hsen, mom, rbbr;
   int8_t bias_adds;
   uint32_t cmask;  // TypeParams::cmask: which inputs are wave-uniform values
+  uint32_t want;   // TypeParams::want: outputs computed though not stored (WantBit)
 };
 
 // The parameter block is not written while a launch runs, so its words may be read in the
@@ -163,7 +164,8 @@ __device__ __forceinline__ Methods type_methods(const TypeParams &tp) {
   const uint64_t w = *cptr(&tp.m_qsur[0]), b = *cptr(&tp.bias_adds);
   return Methods{{byte_of(w, 0), byte_of(w, 1), byte_of(w, 2)}, byte_of(w, 3), byte_of(w, 4),
                  byte_of(w, 5),  byte_of(w, 6), byte_of(w, 7),  byte_of(b, 0),
-                 FCX_CONST_UNIFORM ? (uint32_t)(b >> 32) : 0u};
+                 FCX_CONST_UNIFORM ? (uint32_t)(b >> 32) : 0u,
+                 FCX_SKIP_STORES ? (uint32_t)(uint8_t)(b >> 8) : 0u};
 }
 __device__ __forceinline__ uint32_t type_cmask(const TypeParams &tp) {
   return FCX_CONST_UNIFORM ? (uint32_t)(*cptr(&tp.bias_adds) >> 32) : 0u;
@@ -239,7 +241,7 @@ __device__ __forceinline__ void momentum(int8_t m, bool north, const UVGridPtrs 
                                          const Vec<C, R> &ts, const Vec<C, R> &ps, const Vec<C, R> &u,
                                          const Vec<C, R> &v, const Vec<C, R> &vel, const Vec<C, R> &qs,
                                          const Vec<C, R> &a, int64_t j0, int64_t n, int64_t D_, Emit &emit, int slot) {
-  if (!g.mom) return;
+  // (the callers decide: g.mom is bound, or its value is wanted though not stored -- WantBit)
   Vec<C, R> out;
   if (m == FCX_ZERO) {
     out = splat<C, R>(R(0));
@@ -256,19 +258,21 @@ __device__ __forceinline__ void momentum(int8_t m, bool north, const UVGridPtrs 
   } else {
     return;
   }
-  ST(g.mom, j0, n, out);
+  if (g.mom) ST(g.mom, j0, n, out);
   if (slot >= 0) emit(slot, out);
 }
 
 // QSUR + momentum on one separate u or v grid (non-merged layout).
 // TM = 1: one wait for the grid's inputs before its first store (process, wait_inputs).
-template <int C, bool NT, class R, int TM, bool UNI>
+// SKIP: QSUR of the grid may be wanted (by its momentum) though not stored (Methods::want).
+template <int C, bool NT, class R, int TM, bool UNI, bool SKIP>
 __device__ __forceinline__ void uv_grid(const TypeParams &tp, const Methods &mt, int k, uint32_t stages, int64_t j0,
                                         int64_t n, int64_t D_) {
   const UVGridPtrs &g = tp.uv[k];
   const uint32_t s_qsur = k == 0 ? S_QSUR_U : S_QSUR_V;
   const uint32_t s_mom = k == 0 ? S_UMOM : S_VMOM;
-  const bool do_q = (stages & s_qsur) && mt.qsur[1 + k] == FCX_CCLM && g.qsur;
+  const bool want_q = SKIP && (mt.want & (k == 0 ? W_QSUR_U : W_QSUR_V));
+  const bool do_q = (stages & s_qsur) && mt.qsur[1 + k] == FCX_CCLM && (g.qsur || want_q);
   const bool do_m = (stages & s_mom) && g.mom;
   if (!do_q && !do_m) return;
   Vec<C, R> ts = {}, fi = {}, ps = {}, u = {}, v = {}, a = {}, qs = {};
@@ -289,7 +293,7 @@ __device__ __forceinline__ void uv_grid(const TypeParams &tp, const Methods &mt,
   if constexpr (TM == 1) wait_inputs();
   if (do_q) {
     FOR_C qs.v[i] = qsur_cclm(fi.v[i], ps.v[i], ts.v[i]);
-    ST(g.qsur, j0, n, qs);
+    if (g.qsur) ST(g.qsur, j0, n, qs);
   }
   if (do_m) {
     Vec<C, R> vel;
@@ -472,6 +476,8 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
   // equal even where a value's bits look like an address, and two constants differ by their
   // bits.  h_cm holds the constant bits of the held inputs (wave-uniform, scalar registers).
   constexpr bool kUni = uniform_inputs<R, VAR, RAVG>();
+  // (fcx_internal.h: the planner's rule too)
+  constexpr bool kSkip = skip_family(sizeof(R) == 4, VAR, RAVG, TM == 1, MERGED, HALO);
   uint32_t h_cm = 0, cm = 0;  // cm: the current type's TypeParams::cmask
   auto is_new = [&](const double *ptr_, const double *held, int bit) {
     if constexpr (!kUni) return ptr_ && ptr_ != held;
@@ -542,6 +548,9 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
     const TGridPtrs &g = tp.t;
     const Methods mt = type_methods(tp);
     cm = kUni ? mt.cmask : 0u;
+    // outputs of this type a consumer in the launch wants though their store pointer is null
+    // (wave-uniform, in scalar registers with the method bytes; a compile-time zero elsewhere)
+    const uint32_t want = kSkip ? mt.want : 0u;
     constexpr int8_t kVarMethod = VAR == 1 ? FCX_CCLM : VAR == 2 ? FCX_MOM5 : FCX_RCO;
     const int8_t m_q = VAR ? (VAR == 3 ? FCX_NONE : FCX_CCLM) : mt.qsur[0];
     const int8_t m_qu = VAR ? m_q : mt.qsur[1];
@@ -644,15 +653,17 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
         early();
       }
       // ---- calc_flux_radiation_blackbody (calc:331-343)
-      if ((stages & S_RBBR) && g.rbbr) {
+      // (every flux block below: run when its output is stored OR wanted though not stored --
+      // WantBit --, and only the store is guarded by the pointer)
+      if ((stages & S_RBBR) && (g.rbbr || (want & W_RBBR))) {
         Vec<C, R> r;
         if (mt.rbbr == FCX_STBO) {
           FOR_C r.v[i] = rbbr_stbo(ts.v[i]);
-          ST(g.rbbr, j0, ns, r);
+          if (g.rbbr) ST(g.rbbr, j0, ns, r);
           sink(A_RBBR, r);
         } else if (mt.rbbr == FCX_ZERO) {
           r = zeros<C, R, TM == 1>();
-          ST(g.rbbr, j0, ns, r);
+          if (g.rbbr) ST(g.rbbr, j0, ns, r);
           sink(A_RBBR, r);
         }
       }
@@ -688,22 +699,22 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
         }
       }
       // ---- calc_flux_heat_latent (calc:135-152)
-      if ((stages & S_HLAT) && g.hlat) {
+      if ((stages & S_HLAT) && (g.hlat || (want & W_HLAT))) {
         Vec<C, R> h;
         if (mt.hlat == FCX_WATER) {
           FOR_C h.v[i] = me.v[i] * R(kLv);
-          ST(g.hlat, j0, ns, h);
+          if (g.hlat) ST(g.hlat, j0, ns, h);
         } else if (mt.hlat == FCX_ICE) {
           FOR_C h.v[i] = me.v[i] * R(kLs);
-          ST(g.hlat, j0, ns, h);
+          if (g.hlat) ST(g.hlat, j0, ns, h);
         } else if (mt.hlat == FCX_ZERO) {
           h = zeros<C, R, TM == 1>();
-          ST(g.hlat, j0, ns, h);
+          if (g.hlat) ST(g.hlat, j0, ns, h);
         }
         if (mt.hlat == FCX_WATER || mt.hlat == FCX_ICE || mt.hlat == FCX_ZERO) sink(A_HLAT, h);
       }
       // ---- calc_flux_heat_sensible (calc:167-206), P3: QATM in the q_s slot
-      if ((stages & S_HSEN) && g.hsen) {
+      if ((stages & S_HSEN) && (g.hsen || (want & W_HSEN))) {
         const int8_t m = m_hs;
         Vec<C, R> h;
         if (m == FCX_CCLM || m == FCX_MOM5) {
@@ -715,13 +726,13 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
             const Vec<C, R> &a = (m == FCX_CCLM) ? amoi : chea;
             FOR_C h.v[i] = hsen_cclm(a.v[i], pa.v[i], ps.v[i], qa.v[i], ta.v[i], ts.v[i], vel.v[i]);
           }
-          ST(g.hsen, j0, ns, h);
+          if (g.hsen) ST(g.hsen, j0, ns, h);
         } else if (m == FCX_RCO) {
           FOR_C h.v[i] = hsen_rco(ta.v[i], ts.v[i], vel.v[i]);
-          ST(g.hsen, j0, ns, h);
+          if (g.hsen) ST(g.hsen, j0, ns, h);
         } else if (m == FCX_ZERO) {
           h = zeros<C, R, TM == 1>();
-          ST(g.hsen, j0, ns, h);
+          if (g.hsen) ST(g.hsen, j0, ns, h);
         }
         if (m == FCX_CCLM || m == FCX_MOM5 || m == FCX_RCO || m == FCX_ZERO) sink(A_HSEN, h);
       }
@@ -731,15 +742,16 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
         for (int k = 0; k < 2; ++k) {
           const UVGridPtrs &gk = tp.uv[k];
           const uint32_t s_qsur = k == 0 ? S_QSUR_U : S_QSUR_V;
-          if ((stages & s_qsur) && (k == 0 ? m_qu : m_qv) == FCX_CCLM && gk.qsur) {
+          if ((stages & s_qsur) && (k == 0 ? m_qu : m_qv) == FCX_CCLM &&
+              (gk.qsur || (want & (k == 0 ? W_QSUR_U : W_QSUR_V)))) {
             if (!((stages & S_QSUR_T) && m_q == FCX_CCLM)) {
               FOR_C qs.v[i] = qsur_cclm(fi.v[i], ps.v[i], ts.v[i]);
             }
-            ST(gk.qsur, j0, ns, qs);
+            if (gk.qsur) ST(gk.qsur, j0, ns, qs);
           }
         }
-        const bool do_u = (stages & S_UMOM) && tp.uv[0].mom;
-        const bool do_v = (stages & S_VMOM) && tp.uv[1].mom;
+        const bool do_u = (stages & S_UMOM) && (tp.uv[0].mom || (want & W_UMOM));
+        const bool do_v = (stages & S_VMOM) && (tp.uv[1].mom || (want & W_VMOM));
         if (do_u || do_v) {
           if constexpr (kDerive && VAR == 1) {  // CCLM: the rate from a * vel * p_s formed once
             Vec<C, R> rate;
@@ -748,7 +760,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
               if (!(k ? do_v : do_u)) continue;
               Vec<C, R> out;
               FOR_C out.v[i] = -(rate.v[i] * (k ? v.v[i] : u.v[i]));
-              ST(tp.uv[k].mom, j0, ns, out);
+              if (tp.uv[k].mom) ST(tp.uv[k].mom, j0, ns, out);
               sink(k ? A_VMOM : A_UMOM, out);
             }
           } else {
@@ -762,8 +774,8 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       if ((stages & S_RSDR) && g.rsdr) ST(g.rsdr, j0, ns, rsdd);
     }
     if constexpr (!MERGED) {
-      if (j0 < P->n[1]) uv_grid<C, NT, R, TM, kUni>(tp, mt, 0, stages, j0, P->n[1], D_);
-      if (j0 < P->n[2]) uv_grid<C, NT, R, TM, kUni>(tp, mt, 1, stages, j0, P->n[2], D_);
+      if (j0 < P->n[1]) uv_grid<C, NT, R, TM, kUni, kSkip>(tp, mt, 0, stages, j0, P->n[1], D_);
+      if (j0 < P->n[2]) uv_grid<C, NT, R, TM, kUni, kSkip>(tp, mt, 1, stages, j0, P->n[2], D_);
     }
   }
 #undef HOLD

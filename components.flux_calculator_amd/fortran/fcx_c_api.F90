@@ -12,6 +12,7 @@ MODULE fcx_c_api
   INTEGER(c_int), PARAMETER :: FCX_MEM_HOST = 0, FCX_MEM_DEVICE = 1, FCX_ALLOCATED = 2
   INTEGER(c_int), PARAMETER :: FCX_CORR_CELL_MAJOR = 0, FCX_CORR_MONTH_MAJOR = 1
   INTEGER(c_int), PARAMETER :: FCX_PRECISION_F64 = 0, FCX_PRECISION_F32 = 1
+  INTEGER(c_int), PARAMETER :: FCX_OUT_HOST = 0, FCX_OUT_DEVICE = 1, FCX_OUT_UNREAD = 2
   ! which_* tables (enum fcx_flux)
   INTEGER(c_int), PARAMETER :: FCX_SPEC_VAPOR_SURFACE_T = 0, FCX_SPEC_VAPOR_SURFACE_U = 1, &
                                FCX_SPEC_VAPOR_SURFACE_V = 2, FCX_FLUX_MASS_EVAP = 3, &
@@ -92,6 +93,21 @@ MODULE fcx_c_api
       INTEGER(c_int), VALUE :: surface_type, grid, var
       INTEGER(c_int32_t), INTENT(OUT) :: kind
       INTEGER(c_int) :: fcx_constant_info
+    END FUNCTION
+    ! what the host does with a computed output (FCX_OUT_HOST / FCX_OUT_DEVICE / FCX_OUT_UNREAD): one it
+    ! never sends is kept on the device and, where nothing else reads it, not stored at all
+    FUNCTION fcx_set_output_use(engine, surface_type, grid, var, use) BIND(C, name='fcx_set_output_use')
+      IMPORT :: c_int, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int), VALUE :: surface_type, grid, var, use
+      INTEGER(c_int) :: fcx_set_output_use
+    END FUNCTION
+    FUNCTION fcx_output_info(engine, surface_type, grid, var, kind) BIND(C, name='fcx_output_info')
+      IMPORT :: c_int, c_int32_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int), VALUE :: surface_type, grid, var
+      INTEGER(c_int32_t), INTENT(OUT) :: kind
+      INTEGER(c_int) :: fcx_output_info
     END FUNCTION
     FUNCTION fcx_set_corrections(engine, enabled, init_date, corr, n, layout) BIND(C, name='fcx_set_corrections')
       IMPORT :: c_int, c_int32_t, c_int64_t, c_ptr

@@ -12,6 +12,9 @@
 !   fcx_register_average    for each type-0 output (optional: fused averaging)
 !   fcx_declare_constant    for each input the namelist gave a value (val_*_var_*) instead of
 !                           a sender (optional: the field is then never transferred)
+!   fcx_select_outputs      once, with the host's output_field (optional: the computed fluxes no
+!                           output_field entry sends are neither downloaded nor, where nothing
+!                           else reads them, stored)
 !   fcx_commit_engine       validate + device mirrors
 !   fcx_run_phase           fused coupling-step phase (replaces :902 and :972-991)
 !   fcx_start_phase /       the same phase in two halves: started (inputs taken, launch and
@@ -46,6 +49,7 @@ MODULE flux_calculator_calculate
     PUBLIC fcx_register_abort, fcx_start_phase, fcx_finish_phase, fcx_hand_over_field
     PUBLIC fcx_allocate_field, fcx_free_field
     PUBLIC fcx_declare_constant
+    PUBLIC fcx_select_outputs
 
     TYPE(c_ptr), SAVE :: engine = c_null_ptr
     ! What fcx_attach bound.  The reference subroutines take the bottom model, the type count,
@@ -297,6 +301,49 @@ CONTAINS
         CALL check(fcx_bind_constant(engine, INT(surface_type, c_int), INT(which_grid, c_int), INT(my_idx, c_int), &
                                      REAL(value, c_double)), 'fcx_bind_constant')
     END SUBROUTINE fcx_declare_constant
+
+    ! The outputs the host never sends.  output_field holds what the send_to_* / name_send_*
+    ! tables select (add_output_field, basic:170-284); every other computed flux of surface types
+    ! 1..T -- QSUR is one in every set-up -- is calculated, downloaded and left unread.  Called
+    ! between fcx_attach and fcx_commit_engine, where fcx_declare_constant is called, with the
+    ! host's own output_field and the local_field fcx_attach bound: each computed array that no
+    ! output_field entry points to (compared by address, so uniform and 'copy' aliases count as
+    ! sent) and that is not a regridding source is declared FCX_OUT_UNREAD.  From the commit on
+    ! the engine neither writes nor reads those arrays: the fluxes stay on the device, and where
+    ! nothing but the launch's own registers consumes one it is not stored at all (fcx.h,
+    ! fcx_set_output_use).  A host that reads such an array itself must not call this.
+    SUBROUTINE fcx_select_outputs(num_output_fields, output_field, local_field)
+        INTEGER,                                  INTENT(IN) :: num_output_fields
+        TYPE(io_fields_type),    DIMENSION(:),    INTENT(IN) :: output_field
+        TYPE(local_fields_type), DIMENSION(0:,:), INTENT(IN), TARGET :: local_field
+        INTEGER :: computed(7), s, g, k, v, j
+        LOGICAL :: sent
+        TYPE(c_ptr) :: addr
+        IF (.NOT. c_associated(engine)) CALL contract_error('fcx_select_outputs', 'no flux engine attached')
+        computed = [idx_QSUR, idx_MEVA, idx_HLAT, idx_HSEN, idx_RBBR, idx_UMOM, idx_VMOM]
+        DO s = 1, att_types
+            DO g = 1, 3
+                DO k = 1, SIZE(computed)
+                    v = computed(k)
+                    IF (v < 1 .OR. v > MAX_VARNAMES) CYCLE
+                    IF (.NOT. ASSOCIATED(local_field(s,g)%var(v)%field)) CYCLE
+                    IF (SIZE(local_field(s,g)%var(v)%field) == 0) CYCLE
+                    IF (local_field(s,g)%var(v)%put_to_t_grid .OR. local_field(s,g)%var(v)%put_to_u_grid .OR. &
+                        local_field(s,g)%var(v)%put_to_v_grid) CYCLE
+                    addr = c_loc(local_field(s,g)%var(v)%field(1))
+                    sent = .FALSE.
+                    DO j = 1, MIN(num_output_fields, SIZE(output_field))
+                        IF (.NOT. ASSOCIATED(output_field(j)%field)) CYCLE
+                        IF (SIZE(output_field(j)%field) == 0) CYCLE
+                        IF (c_associated(addr, c_loc(output_field(j)%field(1)))) sent = .TRUE.
+                    ENDDO
+                    IF (sent) CYCLE
+                    CALL check(fcx_set_output_use(engine, INT(s, c_int), INT(g, c_int), INT(v, c_int), FCX_OUT_UNREAD), &
+                               'fcx_set_output_use')
+                ENDDO
+            ENDDO
+        ENDDO
+    END SUBROUTINE fcx_select_outputs
 
     ! output_field(j) with surface_type 0 (flux_calculator.F90:909-918, 999-1008)
     SUBROUTINE fcx_register_average(early, which_grid, my_idx)

@@ -22,6 +22,9 @@ FCX_CORR_MONTH_MAJOR = 1
 FCX_PRECISION_F64 = 0
 FCX_PRECISION_F32 = 1
 FCX_COMM_ID_BYTES = 128
+FCX_OUT_HOST = 0
+FCX_OUT_DEVICE = 1
+FCX_OUT_UNREAD = 2
 
 # every symbol declared in include/fcx.h: (name, restype, argtypes)
 _c = ctypes
@@ -102,6 +105,8 @@ SIGNATURES = [
     ("fcx_abort", _I, [_c.c_char_p]),
     ("fcx_bind_constant", _I, [_P, _I, _I, _I, _c.c_double]),
     ("fcx_constant_info", _I, [_P, _I, _I, _I, _c.POINTER(_I32)]),
+    ("fcx_set_output_use", _I, [_P, _I, _I, _I, _I]),
+    ("fcx_output_info", _I, [_P, _I, _I, _I, _c.POINTER(_I32)]),
 ]
 
 

@@ -20,7 +20,7 @@ class Engine:
 
     def __init__(self, lf: LocalFields, num_surface_types, methods, corrections=None,
                  averages=(), regrid=None, device=0, stream=None, atmos=None, options=None, remaps=None,
-                 lib=None, commit=True, use_constants=True):
+                 lib=None, commit=True, use_constants=True, output_use=None):
         """atmos: exchange -> atmosphere accumulation, dict with
              local   : fcx.parallel.LocalAtmos of this rank
              fields  : [(phase, surface_type, grid, name, out_array[n_atmos])]
@@ -38,7 +38,11 @@ class Engine:
              fcx_bind_constant after their arrays are bound, so the engine never transfers them;
              a recorded field whose array no longer holds the value in every cell (a host that
              wrote it after set-up) stays an ordinary array, with a RuntimeWarning and an entry
-             in Engine.dropped_constants.  False: every field is an array."""
+             in Engine.dropped_constants.  False: every field is an array.
+        output_use: {(surface_type, grid, name): use} declared with fcx_set_output_use after the
+             arrays are bound; use is _lib.FCX_OUT_HOST / FCX_OUT_DEVICE / FCX_OUT_UNREAD or one
+             of "host", "device", "unread".  The arrays of the declared slots are neither written
+             nor read by the engine from the commit on."""
         self.lib = lib if lib is not None else _lib.load()
         self.lf = lf
         self.T = int(num_surface_types)
@@ -82,6 +86,9 @@ class Engine:
                         continue
                     _lib.check(self.lib.fcx_bind_constant(h, s, g, IDX[name], float(value)))
                     self.constants[(s, g, name)] = float(value)
+            self.output_use = {}  # (s, g, name) -> use of the slots declared with fcx_set_output_use
+            for (s, g, name), use in (output_use or {}).items():
+                self.set_output_use(s, g, name, use)
             if corrections is not None:
                 init_date, corr = corrections
                 corr = np.ascontiguousarray(corr, dtype=np.float64)
@@ -268,6 +275,21 @@ class Engine:
         """fcx_bind_constant on an uncommitted engine (commit=False)."""
         _lib.check(self.lib.fcx_bind_constant(self.h, int(s), int(g), IDX[name], float(value)))
         self.constants[(s, g, name)] = float(value)
+
+    OUTPUT_USE = {"host": _lib.FCX_OUT_HOST, "device": _lib.FCX_OUT_DEVICE, "unread": _lib.FCX_OUT_UNREAD}
+
+    def set_output_use(self, s, g, name, use):
+        """fcx_set_output_use on an uncommitted engine: what the host does with a computed output."""
+        use = self.OUTPUT_USE[use] if isinstance(use, str) else int(use)
+        _lib.check(self.lib.fcx_set_output_use(self.h, int(s), int(g), IDX[name], use))
+        self.output_use[(s, g, name)] = use
+
+    def output_info(self, s, g, name):
+        """fcx_output_info: 0 the host reads the output, 1 it is kept in a device array, 2 the
+        last whole-phase plan built for it left its store out."""
+        k = ctypes.c_int32()
+        _lib.check(self.lib.fcx_output_info(self.h, int(s), int(g), IDX[name], ctypes.byref(k)))
+        return k.value
 
     def device_layout(self):
         """(tile, tile_stride) of the engine-owned mirrors: cell j of a device buffer is at

@@ -414,10 +414,28 @@ class FluxCalculatorSetup:
             out.add((0, g, var))
         return sorted(out)
 
-    def engine(self, corrections=None, regrid=None, **kw):
-        """An fcx.Engine over the set-up's local_field (methods, averages, put_to)."""
+    def unsent_outputs(self):
+        """The computed slots (computed_slots) whose array no output_field entry addresses: what
+        the step calculates and the host never sends (add_output_field, basic:170-284, builds
+        output_field from the send_to_* / name_send_* tables only).  An array counts as sent
+        through any slot that holds it (uniform type-0 aliases, 'copy' aliases).  A regridding
+        source is left out: its destination is what is sent, and the regridding reads it."""
+        lf = self.local_field
+        sent = {id(lf.field[f.slot]) for f in self.output_field if f.slot in lf.field}
+        return [slot for slot in self.computed_slots()
+                if id(lf.field[slot]) not in sent and not lf.put_to.get(slot, 0)]
+
+    def engine(self, corrections=None, regrid=None, select_outputs=False, **kw):
+        """An fcx.Engine over the set-up's local_field (methods, averages, put_to).
+        select_outputs: the unsent outputs are declared FCX_OUT_UNREAD (fcx_set_output_use), so
+        they are neither downloaded nor, where nothing else reads them, stored."""
+        from . import _lib
         from .engine import Engine
 
+        if select_outputs:
+            use = {slot: _lib.FCX_OUT_UNREAD for slot in self.unsent_outputs()}
+            use.update(kw.pop("output_use", None) or {})
+            kw["output_use"] = use
         return Engine(self.local_field, self._T, self.methods, corrections=corrections,
                       averages=self.averages(), regrid=regrid, **kw)
 

@@ -138,6 +138,48 @@ int fcx_bind_constant(fcx_engine *e, int surface_type, int grid, int var, double
  * constant in a device array the engine filled itself, at commit for a reader outside the flux
  * pass, later when the first launch that streams it is planned or fcx_device_ptr asks for it */
 int fcx_constant_info(const fcx_engine *e, int surface_type, int grid, int var, int32_t *kind);
+/* What the host does with a computed output (a flux of surface types 1..T, a type-0 average, a
+ * regrid destination).  The reference host sends only the fields its send_to_* / name_send_* tables
+ * select (output_field, flux_calculator.F90:668-768, basic:170-284); an output it never sends
+ * need not cross the host link, and one nobody reads at all need not be stored.  Call before
+ * fcx_commit.  The declaration belongs to the buffer, as a constant's does: it covers EVERY slot
+ * bound to the same address ('copy' aliases, uniform type-0 aliases, a T = 1 type-0 slot pointing at
+ * type 1); where slots of one address are declared differently, FCX_OUT_DEVICE wins.
+ *   FCX_OUT_HOST (default): the output is downloaded into the caller's array, as ever.
+ *   FCX_OUT_DEVICE: the kernels store it into a device array of the engine's own -- valid after
+ *     every run, readable through fcx_device_ptr and by every later engine call -- and it never
+ *     crosses the host link.  From fcx_commit on the caller's array is neither written nor read:
+ *     it is not staged, mapped, given a span or used in place (under zero-copy the buffer is an
+ *     engine device array, not the host array), it has no place in the staging arena, and
+ *     fcx_upload_field of the slot is a no-op; fcx_staging_bytes, fcx_zero_copy_bytes and
+ *     fcx_span_runs count the smaller set.  (A slot bound as FCX_MEM_DEVICE keeps the caller's
+ *     device array: it crosses no link as it is.)
+ *   FCX_OUT_UNREAD: FCX_OUT_DEVICE, plus permission not to store it at all.  A whole-phase launch
+ *     (fcx_run / fcx_step / fcx_run_group of a phase, per pipelined chunk too) whose own registers
+ *     are the output's only consumer gets a null store pointer for it; the flux is still computed
+ *     wherever a later flux of the launch needs it (QSUR -> MEVA / momentum, MEVA -> HLAT, a
+ *     register average, the fused accumulation).  The buffer stays FCX_OUT_DEVICE for good when
+ *     anything outside such a launch reads the array: any regridding of the engine, an average
+ *     that re-reads its fields, the separate accumulation kernel or the crossing-record fix-up
+ *     (a fused launch without halo tiles on a map with crossings keeps its accumulated fields;
+ *     so does every launch of an engine whose host arrays fcx_step could cut into pipeline
+ *     chunks -- set FCX_OPT_PIPELINE_CHUNKS to 1 where the engine only runs whole grids),
+ *     a remap, a 'copy' consumer, a whole-phase launch that reads it without producing it; so
+ *     does a type-0 average.  The per-call subroutines (fcx_calc_*) always store.  A skipped
+ *     store leaves the device array STALE until a launch stores it again: a call that would read
+ *     a stale buffer -- a per-call subroutine, fcx_run_atmos, fcx_device_ptr -- returns
+ *     FCX_E_STATE naming the slot before anything is launched.  The array keeps its reserved
+ *     slot in the device pool, as a constant's does.  fcx_algorithmic_bytes drops the skipped
+ *     stores' bytes and nothing else.
+ * Results in every output the host still reads are those of an engine without declarations, bit
+ * for bit.  A declared slot that is unbound, is a constant, or that no plan writes is a named
+ * FCX_E_STATE error of fcx_plan_check / fcx_commit.  Atmosphere outputs (fcx_add_atmos_field) and
+ * remap outputs are always wanted. */
+enum fcx_output_use { FCX_OUT_HOST = 0, FCX_OUT_DEVICE = 1, FCX_OUT_UNREAD = 2 };
+int fcx_set_output_use(fcx_engine *e, int surface_type, int grid, int var, int use);
+/* after fcx_commit: *kind = 0 the host reads the slot's output; 1 it is kept in a device array;
+ * 2 the last whole-phase plan built for it left its store out */
+int fcx_output_info(const fcx_engine *e, int surface_type, int grid, int var, int32_t *kind);
 /* bias_corrections: lcorrections(E_MASS_EVAP_CORRECTION), init_date, corrections(1,:,:) */
 int fcx_set_corrections(fcx_engine *e, int enabled, int32_t init_date, const double *corr,
                         int64_t n, int layout);
