@@ -321,6 +321,8 @@ struct fcx_engine {
   bool aligned16 = true;
   bool f32 = false;       // FCX_PRECISION_F32: float fields, fp32 kernels
   size_t esize = 8;       // bytes per field element
+  bool f32_math = false;  // FCX_OPT_F32_MATH: an fp32 engine's fluxes computed in double
+  bool wide() const { return f32 && f32_math; }  // (without effect on an fp64 engine)
   // bias corrections (bias_corrections.F90)
   bool lcorr = false;
   int32_t init_date = 0;
@@ -559,6 +561,10 @@ extern "C" int fcx_create(int device, int num_surface_types, const int32_t grid_
   // so that a whole test suite can run with the record layout wherever it applies
   if (const char *v = std::getenv("FCX_ATM_RECORDS"))
     if ((*v == '0' || *v == '1' || *v == '2') && !v[1]) e->atm_records_opt = *v - '0';
+  // FCX_F32_MATH=0|1: the default of FCX_OPT_F32_MATH (an explicit option still wins), so that a
+  // REAL(4) host opts in without a code change
+  if (const char *v = std::getenv("FCX_F32_MATH"))
+    if ((*v == '0' || *v == '1') && !v[1]) e->f32_math = *v == '1';
   *out = e;
   return FCX_OK;
 }
@@ -2772,7 +2778,7 @@ static int commit_compact_map(fcx_engine *e) {
   if (!atm.empty())
     HIP_TRY(hipMemcpy((char *)e->d_atm_seg.p + head, atm.data(), atm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
   if (!compact_map(e->f32, false)) return FCX_OK;
-  const int64_t tc = (int64_t)(e->f32 ? kF32Cpl : 2) * 64, nt = (nx + tc - 1) / tc;
+  const int64_t tc = (int64_t)fused_cpl(e->f32, e->wide()) * 64, nt = (nx + tc - 1) / tc;
   std::vector<int32_t> a0((size_t)nt);
   for (int64_t t = 0; t < nt; ++t) a0[(size_t)t] = e->atm_idx[(size_t)(t * tc)];
   return e->d_atm_tile_a0.upload(a0);
@@ -3017,7 +3023,7 @@ static int copy_bufs(fcx_engine *e, const std::vector<int> &ids, bool h2d, std::
 // fix-up launch): one surface type, on a map whose segments are short enough that `halo`
 // lanes of the next tile's head (at most 1/16 of a wave) cover every crossing
 static int full_range_halo(const fcx_engine *e, const Plan *pl) {
-  const int cpl = e->f32 ? kF32Cpl : 2;
+  const int cpl = fused_cpl(e->f32, e->wide());
   const int h = (e->atm_maxseg - 1 + cpl - 1) / cpl;
   if (e->atm_halo && e->atm_crossings > 0 &&
       (pl->host.num_types == 1 || (FCX_HALO_RAVG && pl->host.ravg_on)) && h >= 1 && h <= (cpl == 4 ? 2 : 4))
@@ -3044,6 +3050,7 @@ static LaunchConfig plan_launch(fcx_engine *e, Plan *pl, int64_t lo, int64_t hi,
   lc.merged = pl->host.merged_uv != 0;
   lc.variant = (e->specialize && lc.merged) ? pl->variant : 0;
   lc.f32 = e->f32;
+  lc.wide = e->wide();
   lc.ravg = pl->host.ravg_on != 0;
   // remap records only from the T=1 specialised fp64 kernels with two cells per lane (the
   // rule plan_fused_records applied when it built the plan)
@@ -3073,7 +3080,7 @@ static int launch_empty_cells(fcx_engine *e, Plan *pl, const LaunchConfig &lc) {
 static int launch_fixup(fcx_engine *e, Plan *pl, const LaunchConfig &lc) {
   if (int r = launch_empty_cells(e, pl, lc)) return r;
   if (e->atm_crossings <= 0 || lc.halo) return FCX_OK;
-  const int r = launch_atmos_fixup(pl->af, pl->host.n_max, lc.f32, e->stream);
+  const int r = launch_atmos_fixup(pl->af, pl->host.n_max, lc.f32, e->stream, lc.wide);
   if (r) return fail(FCX_E_HIP, "atmos_fixup launch: %s", hipGetErrorString((hipError_t)r));
   return FCX_OK;
 }
@@ -3556,6 +3563,7 @@ static int select_group(fcx_engine *const *es, int n, int phase, int32_t t, std:
       if (ok && !mem.empty()) {
         const GroupLaunchMember &f = mem[0];
         ok = e->stream == f.e->stream && e->device == f.e->device && m.lc.f32 == f.lc.f32 &&
+             m.lc.wide == f.lc.wide &&
              m.lc.nontemporal == f.lc.nontemporal && (m.lc.halo > 0) == (f.lc.halo > 0) &&
              m.lc.ravg == f.lc.ravg && (m.pl->host.num_types == 1) == (f.pl->host.num_types == 1);
       }
@@ -3613,7 +3621,7 @@ static void group_members(const GroupLaunchMember *mem, int nm, GroupMember *gm)
     e->rec_plan = nullptr;
     e->rec_written = false;
     fields_taken(e);
-    const int64_t own = (m.lc.f32 ? kF32Cpl : 2) * (64 - m.lc.halo);
+    const int64_t own = fused_cpl(m.lc.f32, m.lc.wide) * (64 - m.lc.halo);
     gm[k] = GroupMember{m.pl->dev.p, m.corr_m, 0, m.lc.variant, 0, m.pl->af};
     gm[k].af.n_tiles = (m.pl->host.n_max + own - 1) / own;
   }
@@ -3647,7 +3655,7 @@ static int launch_group(const GroupLaunchMember *mem, int nm) {
     }
   }
   if (nfx) {
-    const int r2 = launch_atmos_fixup_group(fx, fx_n, nfx, mem[0].lc.f32, mem[0].e->stream);
+    const int r2 = launch_atmos_fixup_group(fx, fx_n, nfx, mem[0].lc.f32, mem[0].e->stream, mem[0].lc.wide);
     if (r2) return fail(FCX_E_HIP, "atmos_fixup_group launch: %s", hipGetErrorString((hipError_t)r2));
   }
   for (int k = 0; k < nm; ++k)
@@ -4155,6 +4163,11 @@ extern "C" int fcx_set_option(fcx_engine *e, int option, int64_t value) {
       if (value < 0 || value > 2) return fail(FCX_E_ARG, "atm_records: 0 never, 1 always, 2 auto");
       e->atm_records_opt = (int)value;
       return FCX_OK;
+    case FCX_OPT_F32_MATH:
+      if (e->committed) return fail(FCX_E_STATE, "f32_math is applied at fcx_commit");
+      if (value < 0 || value > 1) return fail(FCX_E_ARG, "f32_math: 0 float arithmetic, 1 double arithmetic");
+      e->f32_math = value != 0;
+      return FCX_OK;
     case FCX_OPT_TILED_LAYOUT:
       if (e->committed) return fail(FCX_E_STATE, "tiled_layout is applied at fcx_commit");
       e->tiled_opt = value != 0;
@@ -4285,6 +4298,12 @@ extern "C" int fcx_atm_records(const fcx_engine *e, int32_t *on) {
   if (!e || !on) return fail(FCX_E_ARG, "NULL argument");
   if (!e->committed) return fail(FCX_E_STATE, "the atmosphere output layout is decided at fcx_commit");
   *on = e->atm_records ? 1 : 0;
+  return FCX_OK;
+}
+
+extern "C" int fcx_f32_math(const fcx_engine *e, int32_t *on) {
+  if (!e || !on) return fail(FCX_E_ARG, "NULL argument");
+  *on = e->wide() ? 1 : 0;
   return FCX_OK;
 }
 

@@ -133,6 +133,8 @@ enum WantBit : uint32_t {
 // consumes a flux but its store, so it never wants one), and the register-average kernels (they
 // kept their registers, but the T = 2 bench step was slower with it in every process pair).
 // tm1: one surface type fixed at compile time; halo: a launch with halo tiles.
+// (f32: the storage type; an fp32 engine computing in double, FCX_OPT_F32_MATH, goes by the fp32
+// engine's rule: at its two cells per lane the halo kernels hold no scratch with the path.)
 constexpr bool skip_family(bool f32, int variant, bool ravg, bool tm1, bool merged, bool halo) {
   if (!FCX_SKIP_STORES) return false;
   if (ravg) return false;
@@ -243,6 +245,8 @@ struct LaunchConfig {
   bool merged = false;       // u/v grids are the t grid
   int variant = 0;           // 0 generic, 1 CCLM, 2 MOM5, 3 RCO (T=1 specialisations)
   bool f32 = false;          // fp32 fields (FCX_PRECISION_F32): 4 cells per lane
+  bool wide = false;         // ... computed in double (FCX_OPT_F32_MATH; needs f32): the same
+                             // launch shapes, tiles and maps, the F32Wide instantiations
   bool ravg = false;         // register averages in this plan (Params::ravg_on)
   int64_t lo = 0, hi = -1;   // cell range of this launch (lo a multiple of kChunkAlign;
                              // hi < 0: to n_max) -- the pipelined host-bound step
@@ -360,6 +364,18 @@ struct FinishGroup {
 #define FCX_F32_CPL 4
 #endif
 constexpr int kF32Cpl = FCX_F32_CPL;
+// ... and of the wide fused kernels (FCX_OPT_F32_MATH): 2, 8-B lanes of 2 floats in 128-cell
+// tiles.  Their step is bound by the fp64 arithmetic, not by memory: four cells per lane hold
+// 172-197 VGPRs (2 waves per SIMD) and ran the T = 1 group launch in 0.811 ms, two cells per
+// lane fit the 128 of 4 waves and ran it in 0.688 ms (profiles/r13/f32_math/ab/).  The tile
+// size is all that differs from the fp32 engine's launches: the compacted map, the crossing
+// records (indexed by this tile), halo lanes and the fix-up go by it.
+#ifndef FCX_WIDE_CPL
+#define FCX_WIDE_CPL 2
+#endif
+constexpr int kWideCpl = FCX_WIDE_CPL;
+// cells per lane of a fused launch: fp64 2, fp32 kF32Cpl, fp32 computing in double kWideCpl
+constexpr int fused_cpl(bool f32, bool wide) { return !f32 ? 2 : wide ? kWideCpl : kF32Cpl; }
 struct GroupMember {
   const Params *P;        // the member's device parameter block
   const double *corr_m;   // its month slice, or nullptr
@@ -392,7 +408,8 @@ int launch_cells_group(GroupMember *members, int n, const LaunchConfig &lc, void
 
 // the segments carried over a tile boundary: carry of tile t-1 + the head cells of tile t,
 // for every tile of a launch of n_cells (fp32: 256-cell tiles of float fields)
-int launch_atmos_fixup(const AtmosFused &af, int64_t n_cells, bool f32, void *stream);
+// (wide: an fp32 engine computing in double, whose tiles are 64 * kWideCpl cells)
+int launch_atmos_fixup(const AtmosFused &af, int64_t n_cells, bool f32, void *stream, bool wide = false);
 // atmosphere records -> the tile-blocked pool the downloads read: soa[f][tiled(a, tpad)] =
 // rec[a * nf + f], a < n_atmos (fp64; rec and soa 16-B aligned)
 int launch_atm_unpack(const double *rec, double *soa, int64_t n_atmos, int nf, int64_t tpad, void *stream);
@@ -405,7 +422,8 @@ struct FixupGroup {
   int64_t first[kMaxGroup + 1];  // member m's (tile boundary, field) threads: [first[m], first[m+1])
   AtmosFused af[kMaxGroup];
 };
-int launch_atmos_fixup_group(const AtmosFused *afs, const int64_t *n_cells, int n, bool f32, void *stream);
+int launch_atmos_fixup_group(const AtmosFused *afs, const int64_t *n_cells, int n, bool f32, void *stream,
+                             bool wide = false);
 int launch_atmos_finish(const AtmosArgs &a, int32_t n_boundaries, void *stream);
 
 // f32: w, src and dst are float arrays (the reference's single-precision build, where the

@@ -26,12 +26,47 @@
 
 namespace fcx {
 
-// C cells of one lane in the arithmetic type R.  The fp64 path holds 2 cells per lane and
-// the fp32 path 4, so one lane's access to an array is a single 16-B dwordx4 either way.
+// C cells of one lane.  The fp64 path holds 2 cells per lane and the fp32 path 4, so one
+// lane's access to an array is a single 16-B dwordx4 either way.
 template <int C, class R = double>
 struct Vec {
   R v[C];
 };
+
+// The precision of a cell kernel is the pair (storage type S, arithmetic type R).  S is what
+// the arrays, the LDS flux rows and every layout decision (cells per 16 B, tile sizes, the
+// compacted map, which family takes wave-uniform inputs or skips stores) go by; R is what the
+// formulas of fcx_physics.h are instantiated with.  double and float name themselves twice (the
+// fp64 and the fp32 engine); F32Wide is the fp32 engine with FCX_OPT_F32_MATH: float arrays,
+// every flux computed in double from its inputs widened after the load (the inputs stay held
+// as floats, the conversion is exact and free of state) and rounded to float once where it is
+// stored or parked.  A value consumed inside the launch is consumed in double, unrounded.
+struct F32Wide {};
+template <class P>
+struct Prec {
+  using arith = P;
+  using store = P;
+};
+template <>
+struct Prec<F32Wide> {
+  using arith = double;
+  using store = float;
+};
+template <class PR>
+constexpr bool is_wide() { return std::is_same<PR, F32Wide>::value; }
+// x in the element type T (the one rounding of a wide flux on its way to memory, or the exact
+// widening of a loaded float); the same object where the types agree
+template <class T, int C>
+__device__ __forceinline__ const Vec<C, T> &cvt(const Vec<C, T> &x) {
+  return x;
+}
+template <class T, int C, class F, class = typename std::enable_if<!std::is_same<T, F>::value>::type>
+__device__ __forceinline__ Vec<C, T> cvt(const Vec<C, F> &x) {
+  Vec<C, T> r;
+#pragma unroll
+  for (int i = 0; i < C; ++i) r.v[i] = (T)x.v[i];
+  return r;
+}
 
 typedef double d2 __attribute__((ext_vector_type(2)));
 #if FCX_WAVE_TRACE
@@ -126,14 +161,15 @@ __device__ __forceinline__ Vec<C, R> zeros() {
 }
 
 // The parameter block holds every field pointer as double*; in the fp32 engine the same
-// pointers address float arrays, so every access reinterprets them as R*.
+// pointers address float arrays, so every access reinterprets them as S* (the storage type;
+// ST rounds a Vec of the arithmetic type to it).
 #define FOR_C _Pragma("unroll") for (int i = 0; i < C; ++i)
 // Field arrays may be tile-blocked (fcx_internal.h, FCX_OPT_TILED_LAYOUT): cell j is at
 // p + j + D_ with D_ = (j >> kLayoutShift) * tpad, the same shift for every array and for
 // the C cells of one lane (j0 is a multiple of C, C divides the tile).  D_ is in scope
 // wherever these are used; D_ = 0 for contiguous arrays.
-#define LD(p, j, n) ld<C, NT, R>(reinterpret_cast<const R *>(p) + D_, j, n)
-#define ST(p, j, n, ...) st<C, NT, R>(reinterpret_cast<R *>(p) + D_, j, n, __VA_ARGS__)
+#define LD(p, j, n) ld<C, NT, S>(reinterpret_cast<const S *>(p) + D_, j, n)
+#define ST(p, j, n, ...) st<C, NT, S>(reinterpret_cast<S *>(p) + D_, j, n, cvt<S>(__VA_ARGS__))
 
 // The wave-uniform method bytes of one surface type.  gfx950 has no byte-sized scalar load:
 // read as int8_t members, each byte is a vector load, a wait for it (and for every load and
@@ -190,7 +226,7 @@ __device__ __forceinline__ Vec<C, R> ldu(const double *p, bool c, int64_t j0, in
   }
   return ld<C, NT, R>(reinterpret_cast<const R *>(p) + D_, j0, n);
 }
-#define LDU(p, c, j, n) ldu<C, NT, R>(p, c, j, n, D_)
+#define LDU(p, c, j, n) ldu<C, NT, S>(p, c, j, n, D_)
 // The instantiations that take wave-uniform inputs: the fp64 generic and CCLM kernels without
 // register averages.  In the fp32 kernels and the MOM5 and RCO kernels the uniform path cost
 // scratch or a wave per SIMD when it was compiled in (DESIGN.md section 3,
@@ -198,9 +234,9 @@ __device__ __forceinline__ Vec<C, R> ldu(const double *p, bool c, int64_t j0, in
 // the registers but the T = 2 bench step lost 2.6 % with it (profiles/r10/pairs/
 // t2_uniform_in_ravg_kernels.txt).  There the mask is a compile-time zero and the planner
 // binds a constant's filled mirror instead (fcx_engine.hip, build_plan: the same rule).
-template <class R, int VAR, bool RAVG>
+template <class S, int VAR, bool RAVG>
 constexpr bool uniform_inputs() {
-  return uniform_family(sizeof(R) == 4, VAR, RAVG);  // (fcx_internal.h: the planner's rule too)
+  return uniform_family(sizeof(S) == 4, VAR, RAVG);  // (fcx_internal.h: the planner's rule too)
 }
 __device__ __forceinline__ bool cbit(uint32_t m, int bit) { return (m >> bit) & 1u; }
 // The wait of the single-type kernels for a type's inputs: vmcnt(0) alone (expcnt and lgkmcnt
@@ -221,39 +257,39 @@ struct NoEmit {
   __device__ __forceinline__ void operator()(int, const Vec<C, R> &) const {}
 };
 
-template <int C, bool NT, class R, class Emit>
+template <int C, bool NT, class R, class S, class Emit>
 __device__ __forceinline__ void momentum(int8_t m, bool north, const UVGridPtrs &g,
-                                         const Vec<C, R> &ts, const Vec<C, R> &ps, const Vec<C, R> &u,
-                                         const Vec<C, R> &v, const Vec<C, R> &vel, const Vec<C, R> &qs,
-                                         const Vec<C, R> &a, int64_t j0, int64_t n, int64_t D_, Emit &emit, int slot);
+                                         const Vec<C, S> &ts, const Vec<C, S> &ps, const Vec<C, S> &u,
+                                         const Vec<C, S> &v, const Vec<C, R> &vel, const Vec<C, R> &qs,
+                                         const Vec<C, S> &a, int64_t j0, int64_t n, int64_t D_, Emit &emit, int slot);
 
-template <int C, bool NT, class R>
+template <int C, bool NT, class R, class S>
 __device__ __forceinline__ void momentum(int8_t m, bool north, const UVGridPtrs &g,
-                                         const Vec<C, R> &ts, const Vec<C, R> &ps, const Vec<C, R> &u,
-                                         const Vec<C, R> &v, const Vec<C, R> &vel, const Vec<C, R> &qs,
-                                         const Vec<C, R> &a, int64_t j0, int64_t n, int64_t D_) {
+                                         const Vec<C, S> &ts, const Vec<C, S> &ps, const Vec<C, S> &u,
+                                         const Vec<C, S> &v, const Vec<C, R> &vel, const Vec<C, R> &qs,
+                                         const Vec<C, S> &a, int64_t j0, int64_t n, int64_t D_) {
   NoEmit none;
-  momentum<C, NT, R>(m, north, g, ts, ps, u, v, vel, qs, a, j0, n, D_, none, -1);
+  momentum<C, NT, R, S>(m, north, g, ts, ps, u, v, vel, qs, a, j0, n, D_, none, -1);
 }
 
-template <int C, bool NT, class R, class Emit>
+template <int C, bool NT, class R, class S, class Emit>
 __device__ __forceinline__ void momentum(int8_t m, bool north, const UVGridPtrs &g,
-                                         const Vec<C, R> &ts, const Vec<C, R> &ps, const Vec<C, R> &u,
-                                         const Vec<C, R> &v, const Vec<C, R> &vel, const Vec<C, R> &qs,
-                                         const Vec<C, R> &a, int64_t j0, int64_t n, int64_t D_, Emit &emit, int slot) {
+                                         const Vec<C, S> &ts, const Vec<C, S> &ps, const Vec<C, S> &u,
+                                         const Vec<C, S> &v, const Vec<C, R> &vel, const Vec<C, R> &qs,
+                                         const Vec<C, S> &a, int64_t j0, int64_t n, int64_t D_, Emit &emit, int slot) {
   // (the callers decide: g.mom is bound, or its value is wanted though not stored -- WantBit)
   Vec<C, R> out;
   if (m == FCX_ZERO) {
     out = splat<C, R>(R(0));
   } else if (m == FCX_CCLM || m == FCX_MOM5) {
     FOR_C {
-      const R rate = mom_cclm_rate(a.v[i], ps.v[i], qs.v[i], ts.v[i], vel.v[i]);
-      out.v[i] = -(rate * (north ? v.v[i] : u.v[i]));
+      const R rate = mom_cclm_rate<R>(a.v[i], ps.v[i], qs.v[i], ts.v[i], vel.v[i]);
+      out.v[i] = -(rate * R(north ? v.v[i] : u.v[i]));
     }
   } else if (m == FCX_RCO) {
     FOR_C {
-      const R rate = mom_rco_rate(vel.v[i]);
-      out.v[i] = -(rate * (north ? v.v[i] : u.v[i]));
+      const R rate = mom_rco_rate<R>(vel.v[i]);
+      out.v[i] = -(rate * R(north ? v.v[i] : u.v[i]));
     }
   } else {
     return;
@@ -265,7 +301,7 @@ __device__ __forceinline__ void momentum(int8_t m, bool north, const UVGridPtrs 
 // QSUR + momentum on one separate u or v grid (non-merged layout).
 // TM = 1: one wait for the grid's inputs before its first store (process, wait_inputs).
 // SKIP: QSUR of the grid may be wanted (by its momentum) though not stored (Methods::want).
-template <int C, bool NT, class R, int TM, bool UNI, bool SKIP>
+template <int C, bool NT, class R, class S, int TM, bool UNI, bool SKIP>
 __device__ __forceinline__ void uv_grid(const TypeParams &tp, const Methods &mt, int k, uint32_t stages, int64_t j0,
                                         int64_t n, int64_t D_) {
   const UVGridPtrs &g = tp.uv[k];
@@ -275,7 +311,8 @@ __device__ __forceinline__ void uv_grid(const TypeParams &tp, const Methods &mt,
   const bool do_q = (stages & s_qsur) && mt.qsur[1 + k] == FCX_CCLM && (g.qsur || want_q);
   const bool do_m = (stages & s_mom) && g.mom;
   if (!do_q && !do_m) return;
-  Vec<C, R> ts = {}, fi = {}, ps = {}, u = {}, v = {}, a = {}, qs = {};
+  Vec<C, S> ts = {}, fi = {}, ps = {}, u = {}, v = {}, a = {};
+  Vec<C, R> qs = {};
   const uint32_t cm = UNI ? mt.cmask >> (kUvBit0 + kUvBits * k) : 0u;  // this grid's bits
   if (g.tsur || cbit(cm, KU_TSUR)) ts = LDU(g.tsur, cbit(cm, KU_TSUR), j0, n);
   if (g.psur || cbit(cm, KU_PSUR)) ps = LDU(g.psur, cbit(cm, KU_PSUR), j0, n);
@@ -288,17 +325,17 @@ __device__ __forceinline__ void uv_grid(const TypeParams &tp, const Methods &mt,
     if (g.vatm || cbit(cm, KU_VATM)) v = LDU(g.vatm, cbit(cm, KU_VATM), j0, n);
     if (mt.mom == FCX_CCLM && (g.amom || cbit(cm, KU_AMOM))) a = LDU(g.amom, cbit(cm, KU_AMOM), j0, n);
     if (mt.mom == FCX_MOM5 && (g.cmom || cbit(cm, KU_CMOM))) a = LDU(g.cmom, cbit(cm, KU_CMOM), j0, n);
-    if (g.qsur_in && !do_q) qs = LD(g.qsur_in, j0, n);
+    if (g.qsur_in && !do_q) qs = cvt<R>(LD(g.qsur_in, j0, n));
   }
   if constexpr (TM == 1) wait_inputs();
   if (do_q) {
-    FOR_C qs.v[i] = qsur_cclm(fi.v[i], ps.v[i], ts.v[i]);
+    FOR_C qs.v[i] = qsur_cclm<R>(fi.v[i], ps.v[i], ts.v[i]);
     if (g.qsur) ST(g.qsur, j0, n, qs);
   }
   if (do_m) {
     Vec<C, R> vel;
-    FOR_C vel.v[i] = wind(u.v[i], v.v[i]);
-    momentum<C, NT, R>(mt.mom, k == 1, g, ts, ps, u, v, vel, qs, a, j0, n, D_);
+    FOR_C vel.v[i] = wind<R>(u.v[i], v.v[i]);
+    momentum<C, NT, R, S>(mt.mom, k == 1, g, ts, ps, u, v, vel, qs, a, j0, n, D_);
   }
 }
 
@@ -325,12 +362,12 @@ struct AccLds {
 // type-0 accumulator of its slot (type order, from 0.0 -- calc:377-383) and the averages
 // go to the emitter (the fused atmosphere accumulation) once all types are done; without
 // RAVG the value of the single surface type goes to the emitter.
-template <int C, class R, bool RAVG, class Emit>
+template <int C, class R, class S, bool RAVG, class Emit>
 struct Sink {
   const Emit &emit;
   const AvgRegs &ra;
   AccLds<C, R> acc;
-  Vec<C, R> fare;
+  Vec<C, S> fare;
   __device__ __forceinline__ Sink(const Emit &e, const AvgRegs &r, AccLds<C, R> a) : emit(e), ra(r), acc(a) {
     if constexpr (RAVG) {
 #pragma unroll
@@ -338,12 +375,13 @@ struct Sink {
         if (ra.out[k]) acc.set(k, splat<C, R>(R(0)));
     }
   }
-  __device__ __forceinline__ void operator()(int k, const Vec<C, R> &x) {
+  template <class X>  // X: R (a flux just computed) or S (a held input: TSUR)
+  __device__ __forceinline__ void operator()(int k, const Vec<C, X> &x) {
     if constexpr (RAVG) {
       if (ra.out[k]) {
         Vec<C, R> a = acc.get(k);
 #pragma unroll
-        for (int i = 0; i < C; ++i) a.v[i] = a.v[i] + x.v[i] * fare.v[i];
+        for (int i = 0; i < C; ++i) a.v[i] = a.v[i] + R(x.v[i]) * R(fare.v[i]);
         acc.set(k, a);
       }
     } else {
@@ -422,14 +460,21 @@ struct RecEmit {
 // the fused accumulation's products, nothing of them is stored (the next tile's wave stores).
 // early: called once the t-grid inputs of a single-type kernel have landed (TM = 1, after
 // wait_inputs): loads of the caller that depend on values requested with the inputs.
-template <int C, bool MERGED, int VAR, bool NT, class R = double, int TM = 1, bool RAVG = false,
+// PR: the precision (double, float or F32Wide): R its arithmetic and S its storage type.  The
+// inputs are held in S and widened where a formula takes them (the formulas are called as
+// f<R>(...), so a float argument converts on the way in); what the pass computes is held in R.
+template <int C, bool MERGED, int VAR, bool NT, class PR = double, int TM = 1, bool RAVG = false,
           class Emit = NoEmit, bool REC = false, bool HALO = false, class Early = NoEarly>
 __device__ __forceinline__ void process(const Params *__restrict__ P, const double *__restrict__ corr_m,
                                         int64_t j0, const Emit &emit_in = Emit(),
-                                        AccLds<C, R> acc_lds = AccLds<C, R>{nullptr, 0}, int64_t st_end = 0,
-                                        const Early &early = Early()) {
+                                        AccLds<C, typename Prec<PR>::arith> acc_lds =
+                                            AccLds<C, typename Prec<PR>::arith>{nullptr, 0},
+                                        int64_t st_end = 0, const Early &early = Early()) {
+  using R = typename Prec<PR>::arith;
+  using S = typename Prec<PR>::store;
   static_assert(!(RAVG && TM), "register averages need more than one surface type");
   static_assert(!REC || (TM == 1 && !RAVG), "remap records: the T=1 launch");
+  static_assert(!REC || std::is_same<R, S>::value, "remap records: the fp64 engine");
   static_assert(!HALO || (TM == 1 && !RAVG) || (FCX_HALO_RAVG && RAVG), "halo tiles: the T=1 launch");
   const uint32_t stages = P->stages;
   const int T = TM ? 1 : P->num_types;
@@ -442,23 +487,24 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       // (4-B aligned: two scalar words, like type_methods)
       const FCX_CONSTANT word4_t *pw = (const FCX_CONSTANT word4_t *)&P->rec_pos[0];
       const uint64_t posw = (uint64_t)pw[0] | ((uint64_t)pw[1] << 32);
-      return RecEmit<C, R, Emit>{emit_in, reinterpret_cast<R *>(P->rec) + j0 * P->rec_p, P->rec_p, posw,
+      return RecEmit<C, R, Emit>{emit_in, reinterpret_cast<S *>(P->rec) + j0 * P->rec_p, P->rec_p, posw,
                                  (int)max((int64_t)0, min((int64_t)C, ns - j0))};
     } else {
       return emit_in;
     }
   }();
   const int64_t D_ = (j0 >> kLayoutShift) * P->tpad;  // field layout shift of this lane's cells
-  Vec<C, R> corr = {};  // the month slice is a plain contiguous array
-  if (do_t && corr_m && (stages & S_MEVA)) corr = ld<C, NT, R>(reinterpret_cast<const R *>(corr_m), j0, nt);
-  Vec<C, R> rsdd = {};
+  Vec<C, S> corr = {};  // the month slice is a plain contiguous array
+  if (do_t && corr_m && (stages & S_MEVA)) corr = ld<C, NT, S>(reinterpret_cast<const S *>(corr_m), j0, nt);
+  Vec<C, S> rsdd = {};
   if (do_t && P->rsdd0 && (stages & S_RSDR)) rsdd = LD(P->rsdd0, j0, nt);
-  Sink<C, R, RAVG, typename std::remove_cv<typename std::remove_reference<SinkEmit>::type>::type> sink(
+  Sink<C, R, S, RAVG, typename std::remove_cv<typename std::remove_reference<SinkEmit>::type>::type> sink(
       emit, P->ravg, acc_lds);
 
   // inputs held across surface types, with the pointer they were loaded from
-  Vec<C, R> ts = {}, fi = {}, ps = {}, pa = {}, qa = {}, ta = {}, u = {}, v = {}, amoi = {}, cmoi = {},
-            chea = {}, amom = {}, cmom = {}, vel = {};
+  Vec<C, S> ts = {}, fi = {}, ps = {}, pa = {}, qa = {}, ta = {}, u = {}, v = {}, amoi = {}, cmoi = {},
+            chea = {}, amom = {}, cmom = {};
+  Vec<C, R> vel = {};
   const double *h_ts = nullptr, *h_fi = nullptr, *h_ps = nullptr, *h_pa = nullptr, *h_qa = nullptr,
                *h_ta = nullptr, *h_u = nullptr, *h_v = nullptr, *h_amoi = nullptr, *h_cmoi = nullptr,
                *h_chea = nullptr, *h_amom = nullptr, *h_cmom = nullptr;
@@ -475,9 +521,9 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
   // A held input is the pair (member bytes, constant bit): an array and a constant never compare
   // equal even where a value's bits look like an address, and two constants differ by their
   // bits.  h_cm holds the constant bits of the held inputs (wave-uniform, scalar registers).
-  constexpr bool kUni = uniform_inputs<R, VAR, RAVG>();
+  constexpr bool kUni = uniform_inputs<S, VAR, RAVG>();
   // (fcx_internal.h: the planner's rule too)
-  constexpr bool kSkip = skip_family(sizeof(R) == 4, VAR, RAVG, TM == 1, MERGED, HALO);
+  constexpr bool kSkip = skip_family(sizeof(S) == 4, VAR, RAVG, TM == 1, MERGED, HALO);
   uint32_t h_cm = 0, cm = 0;  // cm: the current type's TypeParams::cmask
   auto is_new = [&](const double *ptr_, const double *held, int bit) {
     if constexpr (!kUni) return ptr_ && ptr_ != held;
@@ -521,7 +567,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
   // 1.665 -> 1.628 ms, MOM5 0.616 -> 0.582 ms, CCLM 0.595 -> 0.588 ms)
   constexpr bool kDerive = TM == 0 && (VAR == 1 || VAR == 2);
   Vec<C, R> taef = {}, amv = {}, mvp = {};
-  Vec<C, R> n_ts = {}, n_fi = {}, n_cmoi = {}, n_chea = {}, n_cmom = {}, n_fare = {};
+  Vec<C, S> n_ts = {}, n_fi = {}, n_cmoi = {}, n_chea = {}, n_cmom = {}, n_fare = {};
   auto prefetch = [&](int s2) {
     const TypeParams &q = P->type[s2];
     const uint32_t qm = kUni ? type_cmask(q) : 0u;
@@ -542,7 +588,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
 
   for (int s = 0; s < T; ++s) {
     if constexpr (kReload) {  // no bottom-side input of the previous type stays live
-      ts = fi = cmoi = chea = cmom = Vec<C, R>{};
+      ts = fi = cmoi = chea = cmom = Vec<C, S>{};
     }
     const TypeParams &tp = P->type[s];
     const TGridPtrs &g = tp.t;
@@ -593,30 +639,30 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       if constexpr (!(kDerive && VAR == 1)) HOLDA(amoi, t, amoi, K_AMOI)
       if constexpr (kDerive) {
         if (d_ef) {
-          Vec<C, R> pa_l = {};
+          Vec<C, S> pa_l = {};
           if (g.patm || cbit(cm, K_PATM)) pa_l = LDU(g.patm, cbit(cm, K_PATM), j0, nt);
           h_pa = g.patm;
           hold(K_PATM);
-          FOR_C taef.v[i] = ta_exner(ta.v[i], ps.v[i], pa_l.v[i]);
+          FOR_C taef.v[i] = ta_exner<R>(ta.v[i], ps.v[i], pa_l.v[i]);
         }
         if constexpr (VAR == 1) {
           if (d_amv || d_mvp) {
             Vec<C, R> w;  // the wind speed, only to form the two factors
-            FOR_C w.v[i] = wind(u.v[i], v.v[i]);
+            FOR_C w.v[i] = wind<R>(u.v[i], v.v[i]);
             if (d_amv) {
-              Vec<C, R> am = {};
+              Vec<C, S> am = {};
               if (g.amoi || cbit(cm, K_AMOI)) am = LDU(g.amoi, cbit(cm, K_AMOI), j0, nt);
               h_amoi = g.amoi;
               hold(K_AMOI);
-              FOR_C amv.v[i] = rate_num(am.v[i], w.v[i], ps.v[i]);
+              FOR_C amv.v[i] = rate_num<R>(am.v[i], w.v[i], ps.v[i]);
             }
             if (d_mvp) {
-              Vec<C, R> am = {};
+              Vec<C, S> am = {};
               if (tp.uv[0].amom || cbit(cm, kUvBit0 + KU_AMOM))
                 am = LDU(tp.uv[0].amom, cbit(cm, kUvBit0 + KU_AMOM), j0, nt);
               h_amom = tp.uv[0].amom;
               hold(kUvBit0 + KU_AMOM);
-              FOR_C mvp.v[i] = mom_num(am.v[i], w.v[i], ps.v[i]);
+              FOR_C mvp.v[i] = mom_num<R>(am.v[i], w.v[i], ps.v[i]);
             }
           }
         }
@@ -625,14 +671,14 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
         HOLD(cmoi, t, cmoi, K_CMOI)
         HOLD(chea, t, chea, K_CHEA)
       }
-      if (g.qsur_in) qs = LD(g.qsur_in, j0, nt);  // may be written by this pass: never held
-      if (g.meva_in) me = LD(g.meva_in, j0, nt);
+      if (g.qsur_in) qs = cvt<R>(LD(g.qsur_in, j0, nt));  // may be written by this pass: never held
+      if (g.meva_in) me = cvt<R>(LD(g.meva_in, j0, nt));
       if constexpr (MERGED) {
         if constexpr (!(kDerive && VAR == 1)) HOLDA(amom, uv[0], amom, kUvBit0 + KU_AMOM)
         if constexpr (!kPrefetch) HOLD(cmom, uv[0], cmom, kUvBit0 + KU_CMOM)
       }
       if constexpr (!(kDerive && VAR == 1)) {
-        if (wind_new) FOR_C vel.v[i] = wind(u.v[i], v.v[i]);
+        if (wind_new) FOR_C vel.v[i] = wind<R>(u.v[i], v.v[i]);
       }
       if constexpr (RAVG) {
         if constexpr (!kPrefetch) {
@@ -658,7 +704,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       if ((stages & S_RBBR) && (g.rbbr || (want & W_RBBR))) {
         Vec<C, R> r;
         if (mt.rbbr == FCX_STBO) {
-          FOR_C r.v[i] = rbbr_stbo(ts.v[i]);
+          FOR_C r.v[i] = rbbr_stbo<R>(ts.v[i]);
           if (g.rbbr) ST(g.rbbr, j0, ns, r);
           sink(A_RBBR, r);
         } else if (mt.rbbr == FCX_ZERO) {
@@ -669,7 +715,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       }
       // ---- calc_spec_vapor_surface(t) (calc:37-49)
       if ((stages & S_QSUR_T) && m_q == FCX_CCLM) {
-        FOR_C qs.v[i] = qsur_cclm(fi.v[i], ps.v[i], ts.v[i]);
+        FOR_C qs.v[i] = qsur_cclm<R>(fi.v[i], ps.v[i], ts.v[i]);
         if (g.qsur) ST(g.qsur, j0, ns, qs);
       }
       // ---- calc_flux_mass_evap (calc:75-118), P2: TATM in the T_s slot
@@ -680,19 +726,19 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
           me = zeros<C, R, TM == 1>();
         } else if (m == FCX_CCLM || m == FCX_MOM5) {
           if constexpr (kDerive && VAR == 1) {
-            FOR_C me.v[i] = meva_cclm_num(amv.v[i], qa.v[i], qs.v[i], ta.v[i]);
+            FOR_C me.v[i] = meva_cclm_num<R>(amv.v[i], qa.v[i], qs.v[i], ta.v[i]);
           } else {
-            const Vec<C, R> &a = (m == FCX_CCLM) ? amoi : cmoi;
-            FOR_C me.v[i] = meva_cclm(a.v[i], ps.v[i], qa.v[i], qs.v[i], ta.v[i], vel.v[i]);
+            const Vec<C, S> &a = (m == FCX_CCLM) ? amoi : cmoi;
+            FOR_C me.v[i] = meva_cclm<R>(a.v[i], ps.v[i], qa.v[i], qs.v[i], ta.v[i], vel.v[i]);
           }
         } else if (m == FCX_RCO) {
-          FOR_C me.v[i] = meva_rco(qa.v[i], ts.v[i], vel.v[i]);
+          FOR_C me.v[i] = meva_rco<R>(qa.v[i], ts.v[i], vel.v[i]);
         } else {
           have = false;  // none / copy
         }
         if (have) {
           for (int b = 0; b < mt.bias_adds; ++b) {
-            FOR_C me.v[i] = me.v[i] + corr.v[i];
+            FOR_C me.v[i] = me.v[i] + R(corr.v[i]);
           }
           if (g.meva) ST(g.meva, j0, ns, me);
           sink(A_MEVA, me);
@@ -719,16 +765,16 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
         Vec<C, R> h;
         if (m == FCX_CCLM || m == FCX_MOM5) {
           if constexpr (kDerive && VAR == 1) {
-            FOR_C h.v[i] = hsen_cclm_num(amv.v[i], qa.v[i], ts.v[i], taef.v[i]);
+            FOR_C h.v[i] = hsen_cclm_num<R>(amv.v[i], qa.v[i], ts.v[i], taef.v[i]);
           } else if constexpr (kDerive) {
-            FOR_C h.v[i] = hsen_cclm_num(rate_num(chea.v[i], vel.v[i], ps.v[i]), qa.v[i], ts.v[i], taef.v[i]);
+            FOR_C h.v[i] = hsen_cclm_num<R>(rate_num<R>(chea.v[i], vel.v[i], ps.v[i]), qa.v[i], ts.v[i], taef.v[i]);
           } else {
-            const Vec<C, R> &a = (m == FCX_CCLM) ? amoi : chea;
-            FOR_C h.v[i] = hsen_cclm(a.v[i], pa.v[i], ps.v[i], qa.v[i], ta.v[i], ts.v[i], vel.v[i]);
+            const Vec<C, S> &a = (m == FCX_CCLM) ? amoi : chea;
+            FOR_C h.v[i] = hsen_cclm<R>(a.v[i], pa.v[i], ps.v[i], qa.v[i], ta.v[i], ts.v[i], vel.v[i]);
           }
           if (g.hsen) ST(g.hsen, j0, ns, h);
         } else if (m == FCX_RCO) {
-          FOR_C h.v[i] = hsen_rco(ta.v[i], ts.v[i], vel.v[i]);
+          FOR_C h.v[i] = hsen_rco<R>(ta.v[i], ts.v[i], vel.v[i]);
           if (g.hsen) ST(g.hsen, j0, ns, h);
         } else if (m == FCX_ZERO) {
           h = zeros<C, R, TM == 1>();
@@ -745,7 +791,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
           if ((stages & s_qsur) && (k == 0 ? m_qu : m_qv) == FCX_CCLM &&
               (gk.qsur || (want & (k == 0 ? W_QSUR_U : W_QSUR_V)))) {
             if (!((stages & S_QSUR_T) && m_q == FCX_CCLM)) {
-              FOR_C qs.v[i] = qsur_cclm(fi.v[i], ps.v[i], ts.v[i]);
+              FOR_C qs.v[i] = qsur_cclm<R>(fi.v[i], ps.v[i], ts.v[i]);
             }
             if (gk.qsur) ST(gk.qsur, j0, ns, qs);
           }
@@ -755,18 +801,18 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
         if (do_u || do_v) {
           if constexpr (kDerive && VAR == 1) {  // CCLM: the rate from a * vel * p_s formed once
             Vec<C, R> rate;
-            FOR_C rate.v[i] = mom_cclm_rate_num(mvp.v[i], qs.v[i], ts.v[i]);
+            FOR_C rate.v[i] = mom_cclm_rate_num<R>(mvp.v[i], qs.v[i], ts.v[i]);
             for (int k = 0; k < 2; ++k) {
               if (!(k ? do_v : do_u)) continue;
               Vec<C, R> out;
-              FOR_C out.v[i] = -(rate.v[i] * (k ? v.v[i] : u.v[i]));
+              FOR_C out.v[i] = -(rate.v[i] * R(k ? v.v[i] : u.v[i]));
               if (tp.uv[k].mom) ST(tp.uv[k].mom, j0, ns, out);
               sink(k ? A_VMOM : A_UMOM, out);
             }
           } else {
-            const Vec<C, R> &a = (m_mo == FCX_MOM5) ? cmom : amom;
-            if (do_u) momentum<C, NT, R>(m_mo, false, tp.uv[0], ts, ps, u, v, vel, qs, a, j0, ns, D_, sink, A_UMOM);
-            if (do_v) momentum<C, NT, R>(m_mo, true, tp.uv[1], ts, ps, u, v, vel, qs, a, j0, ns, D_, sink, A_VMOM);
+            const Vec<C, S> &a = (m_mo == FCX_MOM5) ? cmom : amom;
+            if (do_u) momentum<C, NT, R, S>(m_mo, false, tp.uv[0], ts, ps, u, v, vel, qs, a, j0, ns, D_, sink, A_UMOM);
+            if (do_v) momentum<C, NT, R, S>(m_mo, true, tp.uv[1], ts, ps, u, v, vel, qs, a, j0, ns, D_, sink, A_VMOM);
           }
         }
       }
@@ -774,8 +820,8 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       if ((stages & S_RSDR) && g.rsdr) ST(g.rsdr, j0, ns, rsdd);
     }
     if constexpr (!MERGED) {
-      if (j0 < P->n[1]) uv_grid<C, NT, R, TM, kUni, kSkip>(tp, mt, 0, stages, j0, P->n[1], D_);
-      if (j0 < P->n[2]) uv_grid<C, NT, R, TM, kUni, kSkip>(tp, mt, 1, stages, j0, P->n[2], D_);
+      if (j0 < P->n[1]) uv_grid<C, NT, R, S, TM, kUni, kSkip>(tp, mt, 0, stages, j0, P->n[1], D_);
+      if (j0 < P->n[2]) uv_grid<C, NT, R, S, TM, kUni, kSkip>(tp, mt, 1, stages, j0, P->n[2], D_);
     }
   }
 #undef HOLD
@@ -804,9 +850,9 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       if (!ae.x0) continue;  // (plan_audit: every entry binds x0, x[s] and fare[s])
       for (int s = 0; s < T; ++s) {
         if (!ae.x[s] || !ae.fare[s]) continue;
-        const Vec<C, R> x = LD(ae.x[s], j0, n);
-        const Vec<C, R> f = LD(ae.fare[s], j0, n);
-        FOR_C acc.v[i] = acc.v[i] + x.v[i] * f.v[i];
+        const Vec<C, S> x = LD(ae.x[s], j0, n);  // (the stored value, widened)
+        const Vec<C, S> f = LD(ae.fare[s], j0, n);
+        FOR_C acc.v[i] = acc.v[i] + R(x.v[i]) * R(f.v[i]);
       }
       ST(ae.x0, j0, HALO ? min(n, st_end) : n, acc);
     }
@@ -814,17 +860,20 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
 }
 
 // cells [lo, hi) of the plan (lo a multiple of C), grid-stride over C-cell units
-template <int C, bool MERGED, int VAR, bool NT, class R, int TM, bool RAVG, bool REC = false>
-__global__ __launch_bounds__(256, RAVG ? 3 : 1) void cells_kernel(const Params *__restrict__ P,
+template <int C, bool MERGED, int VAR, bool NT, class PR, int TM, bool RAVG, bool REC = false>
+// (wide register averages: 56 KiB of fp64 accumulators per block at 4 cells per lane, 2 blocks per CU)
+__global__ __launch_bounds__(256, RAVG ? (is_wide<PR>() && C == 4 ? 2 : 3) : 1) void cells_kernel(const Params *__restrict__ P,
                                                     const double *__restrict__ corr_m, int64_t lo,
                                                     int64_t hi) {
   const int64_t u_end = (hi + C - 1) / C;
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  // register-average accumulators: [slot][thread][C] (16 B per lane and slot, conflict-free)
+  // register-average accumulators: [slot][thread][C] (16 B per lane and slot, conflict-free;
+  // in the arithmetic type: a wide average is formed from the unrounded fluxes, 32 B per lane)
+  using R = typename Prec<PR>::arith;
   __shared__ R s_acc[RAVG ? kAvgSlots * 256 * C : 1];
   const AccLds<C, R> acc{s_acc + threadIdx.x * C, 256 * C};
   for (int64_t u = lo / C + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u < u_end; u += stride)
-    process<C, MERGED, VAR, NT, R, TM, RAVG, NoEmit, REC>(P, corr_m, u * C, NoEmit(), acc);
+    process<C, MERGED, VAR, NT, PR, TM, RAVG, NoEmit, REC>(P, corr_m, u * C, NoEmit(), acc);
 }
 
 // The T=1 hot path with the exchange -> atmosphere accumulation fused in (AtmosFused).
@@ -867,15 +916,18 @@ constexpr int xrows_doubles() { return kFusedFields * tile_cells<C>() / 2; }
 #define FCX_F32_SEG_ORDINAL 1
 #endif
 constexpr int kSegCap = 192;  // doubles of the list (tile_cells<4>() x (2 + 4) bytes)
-template <class R, int C>
-constexpr bool seg_ordinal() { return FCX_F32_SEG_ORDINAL && sizeof(R) == 4 && C == 4; }
-template <class R, int C>
+// (S: the storage type -- the rows hold what the arrays hold)
+template <class S, int C>
+constexpr bool seg_ordinal() { return FCX_F32_SEG_ORDINAL && sizeof(S) == 4 && C == 4; }
+template <class S, int C>
 constexpr int wave_lds_doubles(int rows) {
-  return sizeof(R) == 4 ? xrows_doubles<C>() + row_len<C>() + (seg_ordinal<R, C>() ? kSegCap : 0)
+  return sizeof(S) == 4 ? xrows_doubles<C>() + row_len<C>() + (seg_ordinal<S, C>() ? kSegCap : 0)
                         : rows * row_len<C>();
 }
 
-template <int C>
+// S: the storage type of the engine's fields.  A flux arrives in the arithmetic type; a float
+// row parks it rounded to float (the value its array holds), whatever it was computed in.
+template <int C, class S = double>
 struct LdsEmitT {
   double *p;    // this wave's [kFusedFields][row_len<C>()] products (fp32: flux rows, weights)
   double w[C];  // the weights of the lane's cells
@@ -884,14 +936,15 @@ struct LdsEmitT {
   __device__ __forceinline__ void operator()(int k, const Vec<CC, R> &x) const {
     static_assert(CC == C, "one emitter per cell width");
     if (FCX_DBG_ATM_NOLDS) return;
-    if constexpr (sizeof(R) == 4 && C == 4) {  // one 16-B store of the lane's four fluxes
+    if constexpr (sizeof(S) == 4 && C == 4) {  // one 16-B store of the lane's four fluxes
       const int lane = threadIdx.x & 63;
       *reinterpret_cast<f4 *>(reinterpret_cast<float *>(p) + k * tile_cells<C>() + C * lane) =
-          f4{x.v[0], x.v[1], x.v[2], x.v[3]};
+          f4{(float)x.v[0], (float)x.v[1], (float)x.v[2], (float)x.v[3]};
       return;
-    } else if constexpr (sizeof(R) == 4 && C == 2) {  // (kF32Cpl 2: one 8-B store)
+    } else if constexpr (sizeof(S) == 4 && C == 2) {  // (kF32Cpl 2: one 8-B store)
       const int lane = threadIdx.x & 63;
-      *reinterpret_cast<f2v *>(reinterpret_cast<float *>(p) + k * tile_cells<C>() + C * lane) = f2v{x.v[0], x.v[1]};
+      *reinterpret_cast<f2v *>(reinterpret_cast<float *>(p) + k * tile_cells<C>() + C * lane) =
+          f2v{(float)x.v[0], (float)x.v[1]};
       return;
     }
 #pragma unroll
@@ -1053,12 +1106,14 @@ constexpr int atmos_waves() { return C == 4 ? FCX_F32_ATMOS_WAVES : FCX_ATMOS_WA
 // products w * x parked in the wave's LDS rows, the segment sums in rounds, the crossing
 // record.  wp: the wave's LDS region.
 // (HALO: 0 no, 1 halo tiles, 2 halo tiles storing per-cell records densely -- record_round)
-template <int C, class R, int VAR, bool NT, int TM, bool RAVG, bool REC, int HALO>
+template <int C, class PR, int VAR, bool NT, int TM, bool RAVG, bool REC, int HALO>
 __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const double *__restrict__ corr_m,
                                            const AtmosFused &af, int64_t tile, double *wp) {
+  using R = typename Prec<PR>::arith;
+  using S = typename Prec<PR>::store;
   constexpr int kT = tile_cells<C>();  // cells per wave tile (lane l: cells C*l .. C*l+C-1)
   constexpr int kR = row_len<C>();
-  constexpr bool kXF = sizeof(R) == 4;  // LDS holds fp32 fluxes + fp64 weights
+  constexpr bool kXF = sizeof(S) == 4;  // LDS holds fp32 fluxes + fp64 weights
   const int64_t n = P->n_max;
   const int own_lanes = HALO ? 64 - af.halo : 64;
   const int64_t kO = (int64_t)C * own_lanes;  // cells a tile owns (HALO: lo == 0)
@@ -1067,7 +1122,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
   const uint64_t above = lane == 63 ? 0ull : (~0ull << (lane + 1));
     const int64_t t0 = tile * kO;
     const int64_t j0 = t0 + C * lane;
-    LdsEmitT<C> emit{wp, {}, lds_slot(C * lane)};
+    LdsEmitT<C, S> emit{wp, {}, lds_slot(C * lane)};
     // the lane's cells in the compacted map: which start a segment (cells past the grid end
     // count as starts: they end the last real segment) and, for those, the segment's
     // atmosphere cell; the lane's C cells share one bit word (j0 is a multiple of C)
@@ -1077,7 +1132,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
     // one 4-B index per cell, loaded with the inputs (the compacted map measured -2.3 % per
     // fp32 step, -0.4 / -1.1 % at T = 1 fp64 and +1.7 % at T = 2 -- its records' first-cell
     // load is a fourth dependent one -- in one process over the same arrays: profiles/r05/seg/)
-    constexpr bool kCompact = compact_map(sizeof(R) == 4, HALO);
+    constexpr bool kCompact = compact_map(sizeof(S) == 4, HALO);
     const int sh = (int)(j0 & 31);
     uint32_t word = 0;
     int32_t before = 0;  // kCompact: segments starting before cell j0
@@ -1140,10 +1195,10 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
     if (j0 < n) {
       const AccLds<C, R> acc{reinterpret_cast<R *>(wp + emit.s), kR};
       if constexpr (kEarly)
-        process<C, true, VAR, NT, R, TM, RAVG, LdsEmitT<C>, REC, (HALO != 0)>(P, corr_m, j0, emit, acc, t0 + kO,
-                                                                             seg_atm_loads);
+        process<C, true, VAR, NT, PR, TM, RAVG, LdsEmitT<C, S>, REC, (HALO != 0)>(P, corr_m, j0, emit, acc, t0 + kO,
+                                                                                  seg_atm_loads);
       else
-        process<C, true, VAR, NT, R, TM, RAVG, LdsEmitT<C>, REC, (HALO != 0)>(P, corr_m, j0, emit, acc, t0 + kO);
+        process<C, true, VAR, NT, PR, TM, RAVG, LdsEmitT<C, S>, REC, (HALO != 0)>(P, corr_m, j0, emit, acc, t0 + kO);
     }
     if constexpr (kXF) {  // the weights row of the fp32 fluxes (dead cells: weight 0)
 #pragma unroll
@@ -1210,7 +1265,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
       for (int q = 0; q < C; ++q) e_end = min(e_end, C * first_bit(m[q] & (q > i ? ge : gt)) + q);
       return min(e_end, kT);
     };
-    if constexpr (seg_ordinal<R, C>()) {
+    if constexpr (seg_ordinal<S, C>()) {
       static_assert(kT == 256 && kSegCap * 8 == kT * 6, "one list entry per cell of the tile");
       uint16_t *seg = reinterpret_cast<uint16_t *>(wp + xrows_doubles<C>() + row_len<C>());  // [kT]
       int32_t *seg_a = reinterpret_cast<int32_t *>(seg + kT);                                 // [kT]
@@ -1240,7 +1295,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
 #pragma unroll
           for (int k = 0; k < kFusedFields; ++k) acc[k] = 0.0;
           for (int e = c; e < end; ++e) add_cell(acc, e);
-          segment_done<R>(af, tile, ai, acc, !HALO && end == kT && next_cont);
+          segment_done<S>(af, tile, ai, acc, !HALO && end == kT && next_cont);
         }
       }
       rem = 0;
@@ -1250,7 +1305,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
     // wave's stores are ONE contiguous run of records (two partial 128-B lines, not two per
     // field).  record_round stores it.
     constexpr bool kDense = HALO == 2;
-    static_assert(!kDense || (sizeof(R) == 8 && C == 2 && !REC && !RAVG), "dense records: the fp64 T = 1 halo launch");
+    static_assert(!kDense || (sizeof(S) == 8 && C == 2 && !REC && !RAVG), "dense records: the fp64 T = 1 halo launch");
     while (__ballot(rem != 0)) {
       if constexpr (kDense) {
         // every lane takes part in record_round, so the sum is written without a branch: a
@@ -1283,7 +1338,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
         for (int k = 0; k < kFusedFields; ++k) acc[k] = 0.0;
         for (int e = c; e < end; ++e) add_cell(acc, e);
         // (HALO: the segment ends inside the wave's own + halo cells by the engine's rule)
-        segment_done<R>(af, tile, ai, acc, !HALO && end == kT && next_cont);
+        segment_done<S>(af, tile, ai, acc, !HALO && end == kT && next_cont);
       }
     }
     // the number of head cells (continuing the previous tile's segment) for
@@ -1319,20 +1374,29 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
     wave_sync();  // every lane is done reading before the next tile overwrites the region
 }
 
+// ... and the wide ones (F32Wide, kWideCpl = 2 cells per lane): 2 = at most 256 VGPRs, which
+// leaves the compiler free -- at two cells per lane they take 79-125 VGPRs, 4 waves or more per
+// SIMD, no scratch (profiles/r13/f32_math/isa/).  At four cells per lane (FCX_WIDE_CPL 4, A/B)
+// they took 172-197 and 2 waves, and 20-88 B of scratch under a cap of 3 blocks.
+#ifndef FCX_WIDE_ATMOS_BLOCKS
+#define FCX_WIDE_ATMOS_BLOCKS 2
+#endif
 template <int C, class R, int VAR, bool NT, int TM, bool RAVG, bool REC = false, int HALO = 0>
 // (REC: the record stores took CCLM to 129 VGPRs and 3 waves per SIMD; capped at 4 blocks = 4 waves)
 __global__ __launch_bounds__(64 * atmos_waves<C>(), RAVG  ? FCX_RAVG_ATMOS_BLOCKS
                                                   : REC ? 4
+                                                  : is_wide<R>() ? FCX_WIDE_ATMOS_BLOCKS
                                                   : (C == 4 && VAR != 3) ? FCX_F32_ATMOS_BLOCKS
                                                                          : FCX_T1_ATMOS_BLOCKS) void cells_atmos_kernel(const Params *__restrict__ P,
                                                           const double *__restrict__ corr_m,
                                                           const AtmosFused af, int64_t lo, int64_t hi) {
-  static_assert(!RAVG || (C == 2 && sizeof(R) == 8), "register averages: fp64 engine only");
-  static_assert(sizeof(R) == 8 || C == 4 || C == 2, "fp32 flux rows: 4 or 2 cells per lane");
+  using S = typename Prec<R>::store;  // (R: the precision -- double, float or F32Wide)
+  static_assert(!RAVG || (C == 2 && sizeof(S) == 8), "register averages: fp64 engine only");
+  static_assert(sizeof(S) == 8 || C == 4 || C == 2, "fp32 flux rows: 4 or 2 cells per lane");
   // product rows [kFusedFields][kR]; with RAVG they first serve as the accumulators of
   // the type-0 averages (slot k = row k, TSUR in an extra row), then hold w * average
   constexpr int kRows = RAVG ? kAvgSlots : kFusedFields;
-  __shared__ double s_p[atmos_waves<C>()][wave_lds_doubles<R, C>(kRows)];
+  __shared__ double s_p[atmos_waves<C>()][wave_lds_doubles<typename Prec<R>::store, C>(kRows)];
   static_assert(!HALO || (TM == 1 && !RAVG) || (FCX_HALO_RAVG && RAVG), "halo tiles: the T=1 launch");
   const int own_lanes = HALO ? 64 - af.halo : 64;
   const int64_t kO = (int64_t)C * own_lanes;  // cells a tile owns (HALO: lo == 0)
@@ -1384,6 +1448,7 @@ __global__ __launch_bounds__(64 * atmos_waves<C>(), RAVG  ? FCX_RAVG_ATMOS_BLOCK
 #endif
 template <int C, class R, bool NT, int HALO, int TM = 1, bool RAVG = false>
 __global__ __launch_bounds__(64 * atmos_waves<C>(), RAVG ? FCX_RAVG_ATMOS_BLOCKS
+                                                    : is_wide<R>() ? FCX_WIDE_ATMOS_BLOCKS
                                                     : C == 4 ? FCX_F32_ATMOS_BLOCKS : FCX_GROUP_BLOCKS) void
 cells_atmos_group_kernel(const GroupArgs g, const Params *__restrict__ P0, const Params *__restrict__ P1,
                          const Params *__restrict__ P2, const Params *__restrict__ P3) {
@@ -1394,7 +1459,7 @@ cells_atmos_group_kernel(const GroupArgs g, const Params *__restrict__ P0, const
   // round trip before the field loads): the group kernel took 1.156 ms against 0.783 ms
   // for the three launches it replaced (a round-4 diagnostic build, not kept).
   constexpr int kRows = RAVG ? kAvgSlots : kFusedFields;
-  __shared__ double s_p[atmos_waves<C>()][wave_lds_doubles<R, C>(kRows)];
+  __shared__ double s_p[atmos_waves<C>()][wave_lds_doubles<typename Prec<R>::store, C>(kRows)];
   const int wv = threadIdx.x >> 6;
   double *wp = s_p[wv];
   const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
@@ -1702,6 +1767,19 @@ __global__ __launch_bounds__(256) void fill_kernel(R *x, int64_t n, R value, int
   }
 }
 
+// The wide instantiations (F32Wide) are compiled in a translation unit of their own
+// (fcx_kernels_wide.hip includes this file with FCX_KERNELS_WIDE_TU set), beside this one: the
+// templates above are shared, each unit instantiates its own precisions, and these three
+// launchers are the seam.  Shapes as computed by launch_cells / launch_cells_group.
+#ifndef FCX_KERNELS_WIDE_TU
+#define FCX_KERNELS_WIDE_TU 0
+#endif
+int launch_wide_fused(int variant, bool halo, bool nt, int blocks, hipStream_t s, const Params *dp,
+                      const double *corr_m, const AtmosFused &af, int64_t lo, int64_t hi);
+void launch_wide_cells(int c, const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
+                       const double *corr_m, int64_t lo, int64_t hi);
+void launch_wide_group(bool nt, bool halo, int blocks, hipStream_t s, const GroupArgs &g);
+
 static int grid_for(int64_t units, int max_blocks = 256 * 8) {
   // memory-bound grid-stride: enough waves to fill 256 CUs, capped (0 = one unit per thread)
   int64_t blocks = (units + 255) / 256;
@@ -1741,6 +1819,7 @@ static void launch_c(const LaunchConfig &lc, int blocks, hipStream_t s, const Pa
   }
 }
 
+#if !FCX_KERNELS_WIDE_TU
 template <int VAR>
 static void launch_rec(bool nt, int blocks, hipStream_t s, const Params *dp, const double *corr_m, int64_t lo,
                        int64_t hi) {
@@ -1752,6 +1831,7 @@ static void launch_rec(bool nt, int blocks, hipStream_t s, const Params *dp, con
                        corr_m, lo, hi);
 }
 
+#endif
 // type mode: one surface type (compile-time), several, several with register averages
 template <int C, class R>
 static void launch_r(const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
@@ -1775,6 +1855,7 @@ static void launch_atm(bool nt, int blocks, hipStream_t s, const Params *dp, con
                        dim3(64 * atmos_waves<C>()), 0, s, dp, corr_m, af, lo, hi);
 }
 
+#if !FCX_KERNELS_WIDE_TU
 // fused accumulation: one surface type (its fluxes), or several with the type-0 averages in
 // registers (what OASIS sends); several types without register averages are not fused
 template <int VAR>
@@ -1782,7 +1863,10 @@ static int launch_atm_r(const Params *hp, const LaunchConfig &lc, int blocks, hi
                         const double *corr_m, const AtmosFused &af, int64_t lo, int64_t hi) {
   const bool halo = lc.halo > 0;
   if (halo && ((hp->num_types != 1 && !(FCX_HALO_RAVG && lc.ravg)) || lo != 0)) return (int)hipErrorInvalidValue;
-  if (hp->num_types == 1 && lc.f32) {  // fp32 engine: 4 cells per lane, T = 1 only
+  if (lc.wide && !lc.f32) return (int)hipErrorInvalidValue;
+  if (hp->num_types == 1 && lc.wide) {  // fp32 engine computing in double: the wide kernels
+    return launch_wide_fused(VAR, halo, lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+  } else if (hp->num_types == 1 && lc.f32) {  // fp32 engine: 4 cells per lane, T = 1 only
     if (halo)
       launch_atm<kF32Cpl, float, VAR, 1, false, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
     else
@@ -1848,7 +1932,7 @@ int launch_cells(const Params *hp, const Params *dp, const double *corr_m, const
   AtmosFused afl;  // this launch's copy: its tile count (and, in trace builds, its trace slot)
   if (atm) {
     afl = *atm;
-    const int64_t own = (lc.f32 ? kF32Cpl : 2) * (64 - lc.halo);
+    const int64_t own = fused_cpl(lc.f32, lc.wide) * (64 - lc.halo);
     afl.n_tiles = (hi + own - 1) / own;
 #if FCX_WAVE_TRACE
     afl.trace = g_trace.base ? g_trace.base + (g_trace.launches++ % g_trace.slots) * g_trace.stride : nullptr;
@@ -1858,8 +1942,8 @@ int launch_cells(const Params *hp, const Params *dp, const double *corr_m, const
   if (atm) {  // fused accumulation: T=1 specialised merged kernel, 2 cells per lane
     // four waves per block (fp32: two), one 128-cell (fp32: 256-cell) tile per wave and trip.  Default: one trip (full
     // grid) -- +2 % per T=1 step over the 8192-block cap, equal at T=2 (profiles/r01/grid_ab)
-    const int64_t kt = (lc.f32 ? kF32Cpl : 2) * (64 - lc.halo);  // cells a wave tile owns
-    const int64_t kw = lc.f32 ? atmos_waves<kF32Cpl>() : atmos_waves<2>();
+    const int64_t kt = fused_cpl(lc.f32, lc.wide) * (64 - lc.halo);  // cells a wave tile owns
+    const int64_t kw = lc.wide ? atmos_waves<kWideCpl>() : lc.f32 ? atmos_waves<kF32Cpl>() : atmos_waves<2>();
     const int64_t tiles = (hi - lo + kt - 1) / kt;
     const int64_t full = (tiles + kw - 1) / kw;
     const int blocks = (int)std::max<int64_t>(1, lc.max_blocks > 0 ? std::min<int64_t>(full, lc.max_blocks) : full);
@@ -1888,7 +1972,10 @@ int launch_cells(const Params *hp, const Params *dp, const double *corr_m, const
     }
     return (int)hipGetLastError();
   }
-  if (lc.f32) {
+  if (lc.wide && !lc.f32) return (int)hipErrorInvalidValue;
+  if (lc.wide) {
+    launch_wide_cells(c, hp, lc, blocks, s, dp, corr_m, lo, hi);
+  } else if (lc.f32) {
     if (c == 4)
       launch_r<4, float>(hp, lc, blocks, s, dp, corr_m, lo, hi);
     else
@@ -1901,6 +1988,7 @@ int launch_cells(const Params *hp, const Params *dp, const double *corr_m, const
   return (int)hipGetLastError();
 }
 
+#endif
 template <int C, class R, bool NT>
 static void launch_group_h(bool halo, bool ravg, int blocks, hipStream_t s, const GroupArgs &g) {
   const Params *p[kMaxGroup];
@@ -1929,6 +2017,7 @@ static void launch_group_h(bool halo, bool ravg, int blocks, hipStream_t s, cons
                        g, p[0], p[1], p[2], p[3]);
 }
 
+#if !FCX_KERNELS_WIDE_TU
 int launch_cells_group(GroupMember *members, int n, const LaunchConfig &lc, void *stream) {
   if (n < 1 || n > kMaxGroup) return (int)hipErrorInvalidValue;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -1947,10 +2036,13 @@ int launch_cells_group(GroupMember *members, int n, const LaunchConfig &lc, void
   g.n_ranges = n;
   g.total_tiles = total;
   if (total == 0) return 0;
-  const int64_t kw = lc.f32 ? atmos_waves<kF32Cpl>() : atmos_waves<2>();
+  const int64_t kw = lc.wide ? atmos_waves<kWideCpl>() : lc.f32 ? atmos_waves<kF32Cpl>() : atmos_waves<2>();
   const int blocks = (int)std::max<int64_t>(1, (total + kw - 1) / kw);
   if (lc.ravg && (lc.f32 || lc.halo > 0)) return (int)hipErrorInvalidValue;
-  if (lc.f32) {
+  if (lc.wide && !lc.f32) return (int)hipErrorInvalidValue;
+  if (lc.wide) {
+    launch_wide_group(lc.nontemporal, lc.halo > 0, blocks, s, g);
+  } else if (lc.f32) {
     if (lc.nontemporal) launch_group_h<kF32Cpl, float, true>(lc.halo > 0, false, blocks, s, g);
     else launch_group_h<kF32Cpl, float, false>(lc.halo > 0, false, blocks, s, g);
   } else {
@@ -2031,13 +2123,15 @@ int launch_atmos_finish_group(const AtmosArgs *as, const int32_t *nbs, int n, vo
   return (int)hipGetLastError();
 }
 
-int launch_atmos_fixup(const AtmosFused &af, int64_t n, bool f32, void *stream) {
-  const int64_t kt = f32 ? tile_cells<kF32Cpl>() : tile_cells<2>();
+int launch_atmos_fixup(const AtmosFused &af, int64_t n, bool f32, void *stream, bool wide) {
+  const int64_t kt = 64 * fused_cpl(f32, wide);
   const int64_t tiles = (n + kt - 1) / kt;
   if (tiles < 2) return 0;
   const int blocks = (int)(((tiles - 1) * kFusedFields + 255) / 256);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (f32)
+  if (f32 && wide)
+    hipLaunchKernelGGL((atmos_fixup_kernel<float, tile_cells<kWideCpl>()>), dim3(blocks), dim3(256), 0, s, af, tiles);
+  else if (f32)
     hipLaunchKernelGGL((atmos_fixup_kernel<float, tile_cells<kF32Cpl>()>), dim3(blocks), dim3(256), 0, s, af, tiles);
   else
     hipLaunchKernelGGL((atmos_fixup_kernel<double, tile_cells<2>()>), dim3(blocks), dim3(256), 0, s, af, tiles);
@@ -2103,9 +2197,9 @@ int launch_atmos_zero(const AtmosFused &af, const int32_t *cells, int64_t n, boo
   return (int)hipGetLastError();
 }
 
-int launch_atmos_fixup_group(const AtmosFused *afs, const int64_t *n_cells, int n, bool f32, void *stream) {
+int launch_atmos_fixup_group(const AtmosFused *afs, const int64_t *n_cells, int n, bool f32, void *stream, bool wide) {
   if (n < 1 || n > kMaxGroup) return (int)hipErrorInvalidValue;
-  const int64_t kt = f32 ? tile_cells<kF32Cpl>() : tile_cells<2>();
+  const int64_t kt = 64 * fused_cpl(f32, wide);
   FixupGroup g{};
   g.n = n;
   for (int m = 0; m < n; ++m) {
@@ -2116,7 +2210,9 @@ int launch_atmos_fixup_group(const AtmosFused *afs, const int64_t *n_cells, int 
   if (g.first[n] == 0) return 0;
   const int blocks = (int)((g.first[n] + 255) / 256);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (f32)
+  if (f32 && wide)
+    hipLaunchKernelGGL((atmos_fixup_group_kernel<float, tile_cells<kWideCpl>()>), dim3(blocks), dim3(256), 0, s, g);
+  else if (f32)
     hipLaunchKernelGGL((atmos_fixup_group_kernel<float, tile_cells<kF32Cpl>()>), dim3(blocks), dim3(256), 0, s, g);
   else
     hipLaunchKernelGGL((atmos_fixup_group_kernel<double, tile_cells<2>()>), dim3(blocks), dim3(256), 0, s, g);
@@ -2135,5 +2231,39 @@ int launch_fill(double *x, int64_t n, double value, bool f32, int64_t tpad, void
   return (int)hipGetLastError();
 }
 
+#else  // FCX_KERNELS_WIDE_TU: the launchers of the F32Wide instantiations
+
+int launch_wide_fused(int variant, bool halo, bool nt, int blocks, hipStream_t s, const Params *dp,
+                      const double *corr_m, const AtmosFused &af, int64_t lo, int64_t hi) {
+#define FCX_WIDE_ATM(VAR)                                                                            \
+  if (halo)                                                                                          \
+    launch_atm<kWideCpl, F32Wide, VAR, 1, false, false, true>(nt, blocks, s, dp, corr_m, af, lo, hi); \
+  else                                                                                               \
+    launch_atm<kWideCpl, F32Wide, VAR, 1, false>(nt, blocks, s, dp, corr_m, af, lo, hi);
+  switch (variant) {
+    case 1: FCX_WIDE_ATM(1) break;
+    case 2: FCX_WIDE_ATM(2) break;
+    case 3: FCX_WIDE_ATM(3) break;
+    default: return (int)hipErrorInvalidValue;
+  }
+#undef FCX_WIDE_ATM
+  return 0;
+}
+
+void launch_wide_cells(int c, const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
+                       const double *corr_m, int64_t lo, int64_t hi) {
+  if (c == 4)
+    launch_r<4, F32Wide>(hp, lc, blocks, s, dp, corr_m, lo, hi);
+  else
+    launch_r<1, F32Wide>(hp, lc, blocks, s, dp, corr_m, lo, hi);
+}
+
+void launch_wide_group(bool nt, bool halo, int blocks, hipStream_t s, const GroupArgs &g) {
+  if (nt)
+    launch_group_h<kWideCpl, F32Wide, true>(halo, false, blocks, s, g);
+  else
+    launch_group_h<kWideCpl, F32Wide, false>(halo, false, blocks, s, g);
+}
+#endif
 
 }  // namespace fcx

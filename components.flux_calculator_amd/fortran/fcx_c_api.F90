@@ -26,7 +26,8 @@ MODULE fcx_c_api
                                FCX_OPT_TILED_LAYOUT = 11, FCX_OPT_REMAP_PACK = 13, &
                                FCX_OPT_HOST_STAGING = 15, FCX_OPT_HOST_THREADS = 16, &
                                FCX_OPT_ATMOS_HALO = 17, FCX_OPT_DEFERRED_SCATTER = 18, &
-                               FCX_OPT_LIB_SPANS = 19, FCX_OPT_ATM_RECORDS = 21
+                               FCX_OPT_LIB_SPANS = 19, FCX_OPT_ATM_RECORDS = 21, &
+                               FCX_OPT_F32_MATH = 22
   ! retired in version 3: accepted by fcx_set_option and ignored
   INTEGER(c_int), PARAMETER :: FCX_OPT_PIN_HOST = 6, FCX_OPT_CARRY_HANDOFF = 14
   ! the RCCL unique id travels between the ranks as these many bytes (MPI_Bcast)
@@ -395,6 +396,13 @@ MODULE fcx_c_api
       TYPE(c_ptr), VALUE :: engine
       INTEGER(c_int32_t), INTENT(OUT) :: on
       INTEGER(c_int) :: fcx_atm_records
+    END FUNCTION
+    ! 1 = an fp32 engine whose fluxes are computed in double (FCX_OPT_F32_MATH / FCX_F32_MATH)
+    FUNCTION fcx_f32_math(engine, on) BIND(C, name='fcx_f32_math')
+      IMPORT :: c_int, c_int32_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int32_t), INTENT(OUT) :: on
+      INTEGER(c_int) :: fcx_f32_math
     END FUNCTION
     ! 1: the boundary-exchange signature agreement before every exchange (0: first of each)
     FUNCTION fcx_comm_verify(comm, every_exchange) BIND(C, name='fcx_comm_verify')

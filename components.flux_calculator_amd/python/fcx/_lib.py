@@ -21,6 +21,7 @@ FCX_CORR_CELL_MAJOR = 0
 FCX_CORR_MONTH_MAJOR = 1
 FCX_PRECISION_F64 = 0
 FCX_PRECISION_F32 = 1
+FCX_OPT_F32_MATH = 22  # an fp32 engine's fluxes computed in double (fcx_set_option)
 FCX_COMM_ID_BYTES = 128
 FCX_OUT_HOST = 0
 FCX_OUT_DEVICE = 1
@@ -98,6 +99,7 @@ SIGNATURES = [
     ("fcx_memcpy", _I, [_P, _P, _c.c_size_t, _I]),
     ("fcx_last_group_size", _I, [_P, _c.POINTER(_I32)]),
     ("fcx_atm_records", _I, [_P, _c.POINTER(_I32)]),
+    ("fcx_f32_math", _I, [_P, _c.POINTER(_I32)]),
     ("fcx_step_async", _I, [_P, _I, _I32]),
     ("fcx_upload_field", _I, [_P, _I, _I, _I]),
     ("fcx_comm_verify", _I, [_P, _I]),

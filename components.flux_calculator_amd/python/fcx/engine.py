@@ -233,7 +233,8 @@ class Engine:
     OPTIONS = {"cells_per_thread": 1, "max_blocks": 2, "nontemporal": 3, "specialize": 4,
                "atmos_in_run": 5, "pipeline_chunks": 7, "pipeline_min_chunk": 8, "zero_copy": 9,
                "timing": 10, "tiled_layout": 11, "remap_pack": 13, "host_staging": 15, "host_threads": 16,
-               "atmos_halo": 17, "deferred_scatter": 18, "lib_spans": 19, "atm_records": 21}
+               "atmos_halo": 17, "deferred_scatter": 18, "lib_spans": 19, "atm_records": 21,
+               "f32_math": _lib.FCX_OPT_F32_MATH}
 
     def run_atmos(self, phase=PHASE_ALL):
         _lib.check(self.lib.fcx_run_atmos(self.h, phase))
@@ -308,6 +309,12 @@ class Engine:
         """True when the atmosphere outputs are kept as per-cell records (fcx_atm_records)."""
         on = ctypes.c_int32()
         _lib.check(self.lib.fcx_atm_records(self.h, ctypes.byref(on)))
+        return bool(on.value)
+
+    def f32_math(self):
+        """True when this is an fp32 engine computing its fluxes in double (fcx_f32_math)."""
+        on = ctypes.c_int32()
+        _lib.check(self.lib.fcx_f32_math(self.h, ctypes.byref(on)))
         return bool(on.value)
 
     def close(self):

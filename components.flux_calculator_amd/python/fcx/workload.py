@@ -39,7 +39,10 @@ class Workload:
         self.offset, self.n = apple_range(self.n_global, self.rank, self.world)
         self.variants = tuple(variants)
         self.types, self.bias, self.precision = int(types), bool(bias), precision
-        f32 = precision == "f32"
+        if precision not in ("f64", "f32", "f32w"):
+            raise ValueError(f"precision {precision!r}: f64, f32 or f32w")
+        # f32w: float arrays like f32, the fluxes computed in double (option f32_math)
+        f32 = precision in ("f32", "f32w")
         dev = torch.device("cuda", device)
         self.dev = dev
         self.stream = stream if stream is not None else torch.cuda.current_stream(dev)
@@ -71,6 +74,8 @@ class Workload:
         # inputs uploaded once, before any timed region: no staging arena (it would pin a host
         # image of every mirror pool for one copy)
         opts = {"atmos_in_run": 0, "timing": 0, "host_staging": 0}
+        if precision == "f32w":
+            opts["f32_math"] = 1
         opts.update(engine_options or {})
         for i, v in enumerate(self.variants):
             c = build_case(v, n=self.n, T=self.types, bias=self.bias, device=case_dev,

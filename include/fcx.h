@@ -232,6 +232,9 @@ int fcx_last_group_size(fcx_engine *e, int32_t *members);
 /* after fcx_commit: 1 when the engine keeps its atmosphere outputs as per-cell records
  * (FCX_OPT_ATM_RECORDS), 0 when as plain arrays */
 int fcx_atm_records(const fcx_engine *e, int32_t *on);
+/* 1 when the engine is an fp32 engine whose fluxes are computed in double (FCX_OPT_F32_MATH, by
+ * the option or the environment's default), 0 otherwise; before fcx_commit: what it would apply */
+int fcx_f32_math(const fcx_engine *e, int32_t *on);
 /* the three above; with host-bound fields pipelined over cell chunks (FCX_OPT_PIPELINE_CHUNKS) */
 int fcx_step(fcx_engine *e, int phase, int32_t current_step_time);
 /* waits for the engine's stream; the caller's host arrays hold the downloaded outputs once it
@@ -473,7 +476,31 @@ enum fcx_option {
                                    memory or used in place.  Applied at fcx_commit; the
                                    environment variable FCX_ATM_RECORDS (0, 1, 2) sets the
                                    default                                                  */
-  FCX_OPT_TILED_LAYOUT = 11     /* engine-owned mirrors tile-blocked (default 1): tiles of
+  FCX_OPT_F32_MATH = 22,        /* arithmetic of an FCX_PRECISION_F32 engine.  0 (default):
+                                   float, as ever.  1: every flux is computed in double from
+                                   its float inputs and rounded to float once where it is
+                                   stored; arrays, layout, transports, constants, output-use
+                                   rules and fcx_algorithmic_bytes are the fp32 engine's.  One
+                                   rule: a value consumed inside the launch that produced it is
+                                   consumed in double, unrounded (QSUR -> MEVA and momentum,
+                                   MEVA (+ bias) -> HLAT, T_a * EF and the exchange-rate
+                                   numerators formed once per cell, a type-0 average formed in
+                                   registers / LDS from the types' fluxes); a value read back
+                                   from an array is the stored float, widened (a per-call
+                                   subroutine, a regridded field, an average that re-reads its
+                                   fields).  Unchanged: the bias slice (rounded to float at
+                                   commit, widened when read), everything outside the flux
+                                   pass (do_regridding in REAL(4), the accumulation kernel,
+                                   fix-up, remaps, record packing, constant fills) and the
+                                   fused accumulation's products w * (double)x32 of the
+                                   float-rounded flux, so an atmosphere output stays the
+                                   sequential fp64 sum of the engine's own stored fluxes,
+                                   rounded once.  No flux is computed in float with it on.
+                                   Accepted and without effect on an fp64 engine.  Applied at
+                                   fcx_commit (FCX_E_STATE afterwards); other values are
+                                   FCX_E_ARG; the environment variable FCX_F32_MATH (0, 1)
+                                   sets the default                                         */
+  FCX_OPT_TILED_LAYOUT = 11    /* engine-owned mirrors tile-blocked (default 1): tiles of
                                    4096 cells, the read-only arrays' tiles interleaved in
                                    one pool and the written arrays' in another, so a wave's
                                    accesses fall in one contiguous region (+8-10 % streaming
