@@ -5,14 +5,16 @@ arm a fresh set of engines is made over the SAME arrays, run and closed again be
 the arms' order rotating from set to set (as outputs_ab.py does).
   t1_group  the T = 1 three-variant group step (CCLM + MOM5 + RCO, 10M cells, random map, the
             fused accumulation), device-resident
-  t2_group  the T = 2 group step, the type-0 averages accumulated (the fp32 arms have no fused
-            multi-type kernel: their engines run one after the other inside fcx_run_group)
+  t2_group  the T = 2 group step, the type-0 averages accumulated in the one group launch (a
+            library from before the fused multi-type fp32 kernels runs the fp32 arms' engines one
+            after the other inside fcx_run_group, each with a second accumulation pass)
   baltic    the Baltic-size host step (MOM5_BALTIC set-up, 32,768 cells per grid, caller heap
             arrays, early + normal phase through fcx_step); wall clock
 The device cases are event-timed fcx_run_group calls over uploaded inputs.  Reported per arm: the
 median ms per launch of every set, the sets' range, Mcells/s of the median (cells x engines per
 launch) and fcx_algorithmic_bytes summed over the engines.
-  python precision_ab.py [SETS] [CELLS]"""
+  python precision_ab.py [SETS] [CELLS] [CASES, comma-separated: t1_group,t2_group,baltic]
+FCX_LIBRARY=path selects another build of the library (a parent build for an A/B)."""
 import json
 import os
 import sys
@@ -34,6 +36,7 @@ VARIANTS = ("CCLM", "MOM5", "RCO")
 FIELDS = (("MEVA", 1), ("HLAT", 1), ("HSEN", 1), ("RBBR", 1), ("UMOM", 2), ("VMOM", 3))
 SETS = int(sys.argv[1]) if len(sys.argv) > 1 else 3
 N = int(sys.argv[2]) if len(sys.argv) > 2 else 10_000_000
+KINDS = tuple(sys.argv[3].split(",")) if len(sys.argv) > 3 else ("t1_group", "t2_group", "baltic")
 WARM, TIMED = 30, 100
 ARMS = ("fp64", "fp32", "fp32_f64math")
 stream = torch.cuda.current_stream()
@@ -127,7 +130,7 @@ def main():
     la = BlockedRandomAtmosMap().local(0, N, 0, 1, N)
     host = inputs_for_bench(N)
     report = {"n": N, "sets": SETS, "warm": WARM, "timed": TIMED, "arms": ARMS, "cases": {}}
-    for kind in ("t1_group", "t2_group", "baltic"):
+    for kind in KINDS:
         run = baltic_case() if kind == "baltic" else device_case(kind, la, host)
         ms = {a: [] for a in ARMS}
         facts = {}

@@ -937,18 +937,19 @@ static bool merge_ok(const fcx_engine *e) {
 }
 
 // The accumulation rides inside the T=1 specialised launch when every registered field of
-// the phase is one of the six fluxes that launch holds in registers (AtmosFused order).
+// the phase is one of the six fluxes that launch holds in registers (AtmosFused order), and
+// inside the multi-type launch with register averages when every registered field is a type-0
+// average held in a register slot -- in every precision (fp64, fp32, fp32 computing in double).
 static void plan_fused_atmos(fcx_engine *e, Plan &pl, uint32_t stages, int phase) {
   pl.atm_fused = false;
   // (segments longer than half a tile, several hundred exchange cells per atmosphere cell,
-  // go to atmos_kernel: one lane summing a long segment would hold up its whole wave; the
-  // fp32 engine uses atmos_kernel too)
-  // (fp32 engine: T = 1 only, the register averages of several types are fp64-only)
+  // go to atmos_kernel in every precision: one lane summing a long segment would hold up its
+  // whole wave)
   // (the maps its launches read: compact_map)
   const bool maps = (!compact_map(e->f32, true) || e->d_atm_seg) && (!compact_map(e->f32, false) || e->d_atm_seg) &&
                     (compact_map(e->f32, true) || e->d_atm_idx) && (compact_map(e->f32, false) || e->d_atm_idx);
   if (!pl.variant || !maps || e->atm_maxseg > kTile / 2 || e->any_regrid || phase <= 0 ||
-      phase >= 1000 || !e->specialize || (e->f32 && e->T >= 2))
+      phase >= 1000 || !e->specialize)
     return;
   const TypeParams &tp = pl.host.type[0];
   AtmosFused af{};
@@ -1134,7 +1135,9 @@ static int ravg_slot(const fcx_engine *e, const Params &P, uint32_t stages, int 
 // unbound).  The kernels guard every load by its own pointer, so an unbound input reads
 // nothing; this check, run on every plan before its first launch, names the case where a
 // method the plan computes would need an input the planner did not bind -- the predicates of
-// process() / uv_grid() in fcx_kernels.hip, restated on the parameter block.
+// process() / uv_grid() in fcx_kernels.hip, restated on the parameter block.  The predicates do
+// not depend on the precision: the fp32 register-average kernels with the fused accumulation
+// load FARE(s) and, for the TSUR slot, TSUR(s) under the same conditions as the fp64 ones.
 // the mirror of a constant, filled once (stream-ordered before whatever reads it)
 static int fill_constant(fcx_engine *e, Buffer &bf) {
   if (bf.filled || bf.n <= 0 || !bf.dev) return FCX_OK;
@@ -3557,8 +3560,9 @@ static int select_group(fcx_engine *const *es, int n, int phase, int32_t t, std:
       if (int r = plan_stale_check(e, m.pl)) return r;
       bool fused = false;
       m.lc = plan_launch(e, m.pl, 0, -1, &fused);
-      // one surface type, or several with the type-0 averages in registers (fp64, no halo)
-      const bool shape = m.pl->host.num_types == 1 || (m.lc.ravg && !m.lc.f32 && m.lc.halo == 0);
+      // one surface type, or several with the type-0 averages in registers (no halo tiles), in
+      // any precision; the members' precision and T = 1-ness must agree (below)
+      const bool shape = m.pl->host.num_types == 1 || (m.lc.ravg && m.lc.halo == 0);
       ok = fused && shape && m.lc.variant >= 1 && !m.lc.rec && m.lc.max_blocks <= 0 && m.pl->host.n_max > 0;
       if (ok && !mem.empty()) {
         const GroupLaunchMember &f = mem[0];
@@ -4304,6 +4308,19 @@ extern "C" int fcx_atm_records(const fcx_engine *e, int32_t *on) {
 extern "C" int fcx_f32_math(const fcx_engine *e, int32_t *on) {
   if (!e || !on) return fail(FCX_E_ARG, "NULL argument");
   *on = e->wide() ? 1 : 0;
+  return FCX_OK;
+}
+
+extern "C" int fcx_fused_accumulation(fcx_engine *e, int phase, int32_t *on) {
+  if (!e || !on) return fail(FCX_E_ARG, "NULL argument");
+  if (phase < 1 || phase > 3) return fail(FCX_E_ARG, "phase %d unknown", phase);
+  if (int r = check(e)) return r;  // (FCX_E_STATE before fcx_commit)
+  Plan *pl;  // the phase's plan, built here if no run has built it yet (as fcx_algorithmic_bytes does)
+  if (int r = get_plan(e, phase_stages(phase), phase, &pl)) return r;
+  // plan_launch's rule for fcx_run's launch over the whole grid, restated: the query leaves the plan alone
+  const bool variant = e->specialize && pl->host.merged_uv != 0 && pl->variant;
+  const bool two_cells = e->aligned16 && e->launch.cells_per_thread == 2;
+  *on = pl->atm_fused && variant && two_cells && pl->host.n_max > 0 ? 1 : 0;
   return FCX_OK;
 }
 

@@ -131,7 +131,10 @@ enum WantBit : uint32_t {
 // halo tiles (20 B of scratch per lane with it), the fp64 generic multi-type kernel of merged
 // grids without register averages (a wave per SIMD at one cell per lane; nothing in that kernel
 // consumes a flux but its store, so it never wants one), and the register-average kernels (they
-// kept their registers, but the T = 2 bench step was slower with it in every process pair).
+// kept their registers, but the T = 2 bench step was slower with it in every process pair; the
+// rule covers the register-average kernels of every precision, the fp32 and wide ones with the
+// fused accumulation included: there an unread output that an average or the accumulation
+// consumes keeps a stored device array).
 // tm1: one surface type fixed at compile time; halo: a launch with halo tiles.
 // (f32: the storage type; an fp32 engine computing in double, FCX_OPT_F32_MATH, goes by the fp32
 // engine's rule: at its two cells per lane the halo kernels hold no scratch with the path.)
@@ -150,7 +153,9 @@ constexpr bool skip_family(bool f32, int variant, bool ravg, bool tm1, bool merg
 // the template arguments of process) and for the planner (build_plan, with the variant and
 // register-average mode its launch will be instantiated with): a set cmask bit in a launch of
 // any other family would be a value's bits read as an address.  fp64 generic (variant 0) and
-// CCLM (1) kernels without register averages; why not the others: DESIGN.md section 3.
+// CCLM (1) kernels without register averages; why not the others: DESIGN.md section 3.  (No
+// register-average kernel takes them, in any precision: a namelist constant of a multi-type
+// launch, fused or not, is an engine-filled array.)
 constexpr bool uniform_family(bool f32, int variant, bool ravg) {
   return FCX_CONST_UNIFORM && !f32 && !ravg && (variant == 0 || variant == 1);
 }
@@ -294,7 +299,9 @@ int launch_atmos_finish_group(const AtmosArgs *as, const int32_t *n_boundaries, 
 // nontemporal: streaming hint on the field loads (off for host-mapped fields)
 int launch_pack_records(const AtmosArgs &a, int64_t n, bool aligned16, bool nontemporal, void *rec, void *stream);
 
-// Exchange -> atmosphere accumulation fused into the T=1 cells kernel.  The six fluxes it
+// Exchange -> atmosphere accumulation fused into the T=1 cells kernel (or, with several types,
+// into the register-average kernel: the type-0 averages instead of the fluxes; fp64, fp32 and
+// fp32 computing in double alike).  The six fluxes it
 // can take from registers, in this order: MEVA HLAT HSEN RBBR UMOM VMOM (out[k] nullptr =
 // not accumulated).  Every 128-cell wave tile sums the segments that start in it; a
 // segment running past the tile end leaves its prefix sum in the next tile's crossing
@@ -350,7 +357,8 @@ struct AtmosFused {
   uint64_t *trace;     // per wave (dispatch order): {start, end, HW_ID, XCC_ID}, or nullptr
 #endif
 };
-// Several engines' fused T = 1 launches in ONE launch (fcx_run_group): member k's wave tiles
+// Several engines' fused launches (T = 1, or several types with register averages) in ONE launch
+// (fcx_run_group): member k's wave tiles
 // are tiles [tile0, tile0 + af.n_tiles) of the grid.  Passed by value (kernel arguments).
 constexpr int kMaxGroup = 4;
 struct FinishGroup {

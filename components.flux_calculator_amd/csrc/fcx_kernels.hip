@@ -232,7 +232,9 @@ __device__ __forceinline__ Vec<C, R> ldu(const double *p, bool c, int64_t j0, in
 // scratch or a wave per SIMD when it was compiled in (DESIGN.md section 3,
 // profiles/r10/isa/registers_uniform_everywhere.txt); in the register-average kernels it fit
 // the registers but the T = 2 bench step lost 2.6 % with it (profiles/r10/pairs/
-// t2_uniform_in_ravg_kernels.txt).  There the mask is a compile-time zero and the planner
+// t2_uniform_in_ravg_kernels.txt; the fp32 and wide register-average kernels with the fused
+// accumulation are register-average kernels like the others).  There the mask is a
+// compile-time zero and the planner
 // binds a constant's filled mirror instead (fcx_engine.hip, build_plan: the same rule).
 template <class S, int VAR, bool RAVG>
 constexpr bool uniform_inputs() {
@@ -455,7 +457,8 @@ struct RecEmit {
 // differs from the previous type's (wave-uniform scalar compare).  Inputs are never written
 // by the pass, so a held value is the array's value.
 // TM: 1 = one surface type, fixed at compile time (the held inputs and the type loop
-// vanish); 0 = T from the parameter block.  RAVG (register averages) needs TM = 0.
+// vanish); 0 = T from the parameter block.  RAVG (register averages) needs TM = 0; every
+// precision has it, with and without the fused accumulation.
 // HALO: cells at or past st_end are a halo tile's head cells -- their fluxes are computed for
 // the fused accumulation's products, nothing of them is stored (the next tile's wave stores).
 // early: called once the t-grid inputs of a single-type kernel have landed (TM = 1, after
@@ -586,7 +589,16 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
     if (do_t) prefetch(0);
   }
 
-  for (int s = 0; s < T; ++s) {
+  // The wide fused register-average kernels: the type index said wave-uniform to the compiler
+  // (readfirstlane, as cells_atmos_group_kernel says of its member index).  Left to itself it
+  // kept the loop counter of these instantiations in a VGPR, and every pointer of P->type[s] --
+  // the inputs' and outputs' addresses, the next type's for the prefetch -- was an 8-B vector
+  // load from the parameter block with a full vmcnt(0) wait behind it, a dependent round trip
+  // per array: 75 vector loads per wave and type pair where the fp64 kernel issues 22, and a
+  // T = 2 group launch of 2.065 ms against the fp64 engine's 1.571.
+  constexpr bool kUniformType = RAVG && is_wide<PR>() && !std::is_same<Emit, NoEmit>::value;
+  for (int s_ = 0; s_ < T; ++s_) {
+    const int s = kUniformType ? __builtin_amdgcn_readfirstlane(s_) : s_;
     if constexpr (kReload) {  // no bottom-side input of the previous type stays live
       ts = fi = cmoi = chea = cmom = Vec<C, S>{};
     }
@@ -901,8 +913,21 @@ __device__ __forceinline__ int lds_slot(int e) { return e + 2 * (e >> 4); }
 // rows of tile_cells<C>() floats, and one row of weights (fp64, lds_slot layout) behind them;
 // the segment sums form w * (double)x as they read them -- the same products in the same
 // order, in 4 instead of 6 row-lengths of fp64 per wave (more waves per CU).
+// Several types with register averages (RAVG): the accumulators of the type-0 averages live in
+// the same region, and a lane's write of its row entry may touch only what that lane has read.
+//  - float arithmetic (PR = float): an accumulator is C floats, exactly the lane's row entry, so
+//    the accumulators ARE the rows -- slot k of lane l at float k * tile_cells + C * l, TSUR's
+//    slot 6 a seventh row -- and parking the average of slot k overwrites the lane's own
+//    accumulator k in place.  The weights row and the segment list sit behind the seventh row.
+//  - double arithmetic on float rows (F32Wide): an accumulator is C doubles, twice its row
+//    entry, so a row write would land on other lanes' accumulators; the accumulators get a region
+//    of their own behind everything else ([kAvgSlots][64 lanes][C] doubles), the six rows, the
+//    weights row and the list stay where the single-type kernels have them.
+// xrows: the float rows in front of the weights row (kFusedFields, or kAvgSlots in place).
+template <class PR, bool RAVG>
+constexpr int flux_rows() { return RAVG && !is_wide<PR>() ? kAvgSlots : kFusedFields; }
 template <int C>
-constexpr int xrows_doubles() { return kFusedFields * tile_cells<C>() / 2; }
+constexpr int xrows_doubles(int xrows = kFusedFields) { return xrows * tile_cells<C>() / 2; }
 // fp32 (C = 4, up to 4 segment starts per lane): the tile's segments are summed by ordinal --
 // segment s of the tile by lane s % 64 in round s / 64 -- so that each round's atmosphere
 // stores are ONE contiguous run of atmosphere cells per field.  Summed by the lane holding
@@ -919,10 +944,23 @@ constexpr int kSegCap = 192;  // doubles of the list (tile_cells<4>() x (2 + 4) 
 // (S: the storage type -- the rows hold what the arrays hold)
 template <class S, int C>
 constexpr bool seg_ordinal() { return FCX_F32_SEG_ORDINAL && sizeof(S) == 4 && C == 4; }
-template <class S, int C>
-constexpr int wave_lds_doubles(int rows) {
-  return sizeof(S) == 4 ? xrows_doubles<C>() + row_len<C>() + (seg_ordinal<S, C>() ? kSegCap : 0)
-                        : rows * row_len<C>();
+// float rows: the doubles in front of the wide kernels' accumulator region (rows, weights, list)
+template <class PR, int C, bool RAVG>
+constexpr int acc_region_doubles() {
+  return xrows_doubles<C>(flux_rows<PR, RAVG>()) + row_len<C>() +
+         (seg_ordinal<typename Prec<PR>::store, C>() ? kSegCap : 0);
+}
+// one wave's LDS region.  fp64 rows: the product rows, which first serve as the accumulators
+// (slot k = row k, TSUR in a seventh row).  float rows: see flux_rows.
+template <class PR, int C, bool RAVG>
+constexpr int wave_lds_doubles() {
+  if (sizeof(typename Prec<PR>::store) == 8) return (RAVG ? kAvgSlots : kFusedFields) * row_len<C>();
+  return acc_region_doubles<PR, C, RAVG>() + (RAVG && is_wide<PR>() ? kAvgSlots * 64 * C : 0);
+}
+// blocks per CU x waves x bytes per wave of a fused kernel fit the CU's 160 KiB of LDS
+template <class PR, int C, bool RAVG>
+constexpr bool lds_fits(int blocks, int waves) {
+  return (int64_t)blocks * waves * wave_lds_doubles<PR, C, RAVG>() * 8 <= 160 * 1024;
 }
 
 // S: the storage type of the engine's fields.  A flux arrives in the arithmetic type; a float
@@ -1114,6 +1152,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
   constexpr int kT = tile_cells<C>();  // cells per wave tile (lane l: cells C*l .. C*l+C-1)
   constexpr int kR = row_len<C>();
   constexpr bool kXF = sizeof(S) == 4;  // LDS holds fp32 fluxes + fp64 weights
+  constexpr int kWOff = xrows_doubles<C>(flux_rows<PR, RAVG>());  // float rows: the weights row
   const int64_t n = P->n_max;
   const int own_lanes = HALO ? 64 - af.halo : 64;
   const int64_t kO = (int64_t)C * own_lanes;  // cells a tile owns (HALO: lo == 0)
@@ -1193,7 +1232,17 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
     };
     constexpr bool kEarly = kCompact && TM == 1 && FCX_INPUT_WAIT && FCX_EARLY_SEG_ATM;
     if (j0 < n) {
-      const AccLds<C, R> acc{reinterpret_cast<R *>(wp + emit.s), kR};
+      // the lane's accumulators (RAVG; flux_rows): fp64 rows -- slot k is the lane's entry of
+      // product row k; float rows, float arithmetic -- slot k is the lane's entry of flux row k;
+      // float rows, double arithmetic -- a region of its own behind the rows, weights and list
+      const AccLds<C, R> acc = [&]() {
+        if constexpr (!kXF)
+          return AccLds<C, R>{reinterpret_cast<R *>(wp + emit.s), kR};
+        else if constexpr (sizeof(R) == 4)
+          return AccLds<C, R>{reinterpret_cast<R *>(wp) + C * lane, kT};
+        else
+          return AccLds<C, R>{wp + acc_region_doubles<PR, C, RAVG>() + C * lane, 64 * C};
+      }();
       if constexpr (kEarly)
         process<C, true, VAR, NT, PR, TM, RAVG, LdsEmitT<C, S>, REC, (HALO != 0)>(P, corr_m, j0, emit, acc, t0 + kO,
                                                                                   seg_atm_loads);
@@ -1203,13 +1252,13 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
     if constexpr (kXF) {  // the weights row of the fp32 fluxes (dead cells: weight 0)
 #pragma unroll
       for (int h = 0; h < C / 2; ++h)
-        *reinterpret_cast<d2 *>(wp + xrows_doubles<C>() + emit.s + 2 * h) = d2{emit.w[2 * h], emit.w[2 * h + 1]};
+        *reinterpret_cast<d2 *>(wp + kWOff + emit.s + 2 * h) = d2{emit.w[2 * h], emit.w[2 * h + 1]};
     }
     // cell e of the tile added to a segment sum, in link order: its products w * x
     auto add_cell = [&](double *acc, int e) {
       if constexpr (kXF) {
         const float *xr = reinterpret_cast<const float *>(wp);
-        const double we = wp[xrows_doubles<C>() + lds_slot(e)];
+        const double we = wp[kWOff + lds_slot(e)];
 #pragma unroll
         for (int k = 0; k < kFusedFields; ++k) acc[k] = acc[k] + we * (double)xr[k * kT + e];
       } else {
@@ -1267,7 +1316,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
     };
     if constexpr (seg_ordinal<S, C>()) {
       static_assert(kT == 256 && kSegCap * 8 == kT * 6, "one list entry per cell of the tile");
-      uint16_t *seg = reinterpret_cast<uint16_t *>(wp + xrows_doubles<C>() + row_len<C>());  // [kT]
+      uint16_t *seg = reinterpret_cast<uint16_t *>(wp + kWOff + row_len<C>());  // [kT]
       int32_t *seg_a = reinterpret_cast<int32_t *>(seg + kT);                                 // [kT]
       const uint64_t lower = (1ull << lane) - 1;
       int total = 0, o = 0;  // the tile's segments; this lane's first one's ordinal
@@ -1359,7 +1408,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
         double hp[kFusedFields];
         if constexpr (kXF) {
           const float *xr = reinterpret_cast<const float *>(wp);
-          const double we = wp[xrows_doubles<C>() + lds_slot(lane)];
+          const double we = wp[kWOff + lds_slot(lane)];
 #pragma unroll
           for (int k = 0; k < kFusedFields; ++k) hp[k] = we * (double)xr[k * kT + lane];
         } else {
@@ -1391,12 +1440,13 @@ __global__ __launch_bounds__(64 * atmos_waves<C>(), RAVG  ? FCX_RAVG_ATMOS_BLOCK
                                                           const double *__restrict__ corr_m,
                                                           const AtmosFused af, int64_t lo, int64_t hi) {
   using S = typename Prec<R>::store;  // (R: the precision -- double, float or F32Wide)
-  static_assert(!RAVG || (C == 2 && sizeof(S) == 8), "register averages: fp64 engine only");
-  static_assert(sizeof(S) == 8 || C == 4 || C == 2, "fp32 flux rows: 4 or 2 cells per lane");
+  static_assert(sizeof(S) == 8 ? C == 2 : (C == 4 || C == 2), "fp64 rows: 2 cells per lane; fp32 flux rows: 4 or 2");
   // product rows [kFusedFields][kR]; with RAVG they first serve as the accumulators of
   // the type-0 averages (slot k = row k, TSUR in an extra row), then hold w * average
-  constexpr int kRows = RAVG ? kAvgSlots : kFusedFields;
-  __shared__ double s_p[atmos_waves<C>()][wave_lds_doubles<typename Prec<R>::store, C>(kRows)];
+  // (float rows: the averages themselves; their accumulators: flux_rows)
+  __shared__ double s_p[atmos_waves<C>()][wave_lds_doubles<R, C, RAVG>()];
+  static_assert(!RAVG || lds_fits<R, C, RAVG>(FCX_RAVG_ATMOS_BLOCKS, atmos_waves<C>()),
+                "register averages: the launch bound's blocks per CU hold at most 160 KiB of LDS");
   static_assert(!HALO || (TM == 1 && !RAVG) || (FCX_HALO_RAVG && RAVG), "halo tiles: the T=1 launch");
   const int own_lanes = HALO ? 64 - af.halo : 64;
   const int64_t kO = (int64_t)C * own_lanes;  // cells a tile owns (HALO: lo == 0)
@@ -1442,7 +1492,7 @@ __global__ __launch_bounds__(64 * atmos_waves<C>(), RAVG  ? FCX_RAVG_ATMOS_BLOCK
 // Blocks per CU the fp64 T = 1 group kernel is compiled for: 4 = 128 VGPRs, 4 waves per SIMD
 // like the members' own kernels (left free, the three inlined bodies take 139-146 VGPRs and
 // 3 waves; at 128 one 8-B value of the preamble spills: one store and two reloads per wave).
-// The multi-type group (RAVG) keeps the members' FCX_RAVG_ATMOS_BLOCKS.
+// The multi-type group (RAVG) keeps the members' FCX_RAVG_ATMOS_BLOCKS, in every precision.
 #ifndef FCX_GROUP_BLOCKS
 #define FCX_GROUP_BLOCKS 4
 #endif
@@ -1458,8 +1508,9 @@ cells_atmos_group_kernel(const GroupArgs g, const Params *__restrict__ P0, const
   // pointer out of the argument struct, every field was a vector load (and a dependent
   // round trip before the field loads): the group kernel took 1.156 ms against 0.783 ms
   // for the three launches it replaced (a round-4 diagnostic build, not kept).
-  constexpr int kRows = RAVG ? kAvgSlots : kFusedFields;
-  __shared__ double s_p[atmos_waves<C>()][wave_lds_doubles<typename Prec<R>::store, C>(kRows)];
+  __shared__ double s_p[atmos_waves<C>()][wave_lds_doubles<R, C, RAVG>()];
+  static_assert(!RAVG || lds_fits<R, C, RAVG>(FCX_RAVG_ATMOS_BLOCKS, atmos_waves<C>()),
+                "register averages: the launch bound's blocks per CU hold at most 160 KiB of LDS");
   const int wv = threadIdx.x >> 6;
   double *wp = s_p[wv];
   const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
@@ -1774,11 +1825,11 @@ __global__ __launch_bounds__(256) void fill_kernel(R *x, int64_t n, R value, int
 #ifndef FCX_KERNELS_WIDE_TU
 #define FCX_KERNELS_WIDE_TU 0
 #endif
-int launch_wide_fused(int variant, bool halo, bool nt, int blocks, hipStream_t s, const Params *dp,
+int launch_wide_fused(int variant, bool halo, bool ravg, bool nt, int blocks, hipStream_t s, const Params *dp,
                       const double *corr_m, const AtmosFused &af, int64_t lo, int64_t hi);
 void launch_wide_cells(int c, const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
                        const double *corr_m, int64_t lo, int64_t hi);
-void launch_wide_group(bool nt, bool halo, int blocks, hipStream_t s, const GroupArgs &g);
+void launch_wide_group(bool nt, bool halo, bool ravg, int blocks, hipStream_t s, const GroupArgs &g);
 
 static int grid_for(int64_t units, int max_blocks = 256 * 8) {
   // memory-bound grid-stride: enough waves to fill 256 CUs, capped (0 = one unit per thread)
@@ -1857,7 +1908,8 @@ static void launch_atm(bool nt, int blocks, hipStream_t s, const Params *dp, con
 
 #if !FCX_KERNELS_WIDE_TU
 // fused accumulation: one surface type (its fluxes), or several with the type-0 averages in
-// registers (what OASIS sends); several types without register averages are not fused
+// registers (what OASIS sends), in every precision; several types without register averages
+// are not fused
 template <int VAR>
 static int launch_atm_r(const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
                         const double *corr_m, const AtmosFused &af, int64_t lo, int64_t hi) {
@@ -1865,14 +1917,16 @@ static int launch_atm_r(const Params *hp, const LaunchConfig &lc, int blocks, hi
   if (halo && ((hp->num_types != 1 && !(FCX_HALO_RAVG && lc.ravg)) || lo != 0)) return (int)hipErrorInvalidValue;
   if (lc.wide && !lc.f32) return (int)hipErrorInvalidValue;
   if (hp->num_types == 1 && lc.wide) {  // fp32 engine computing in double: the wide kernels
-    return launch_wide_fused(VAR, halo, lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
-  } else if (hp->num_types == 1 && lc.f32) {  // fp32 engine: 4 cells per lane, T = 1 only
+    return launch_wide_fused(VAR, halo, false, lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+  } else if (hp->num_types == 1 && lc.f32) {  // fp32 engine: 4 cells per lane
     if (halo)
       launch_atm<kF32Cpl, float, VAR, 1, false, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
     else
       launch_atm<kF32Cpl, float, VAR, 1, false>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
-  } else if (lc.f32) {
-    return (int)hipErrorInvalidValue;
+  } else if (lc.f32) {  // several types: the register averages, crossing records (no halo tiles)
+    if (!lc.ravg || halo) return (int)hipErrorInvalidValue;
+    if (lc.wide) return launch_wide_fused(VAR, false, true, lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+    launch_atm<kF32Cpl, float, VAR, 0, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
   } else if (hp->num_types == 1 && lc.rec) {
     if (halo)
       launch_atm<2, double, VAR, 1, false, true, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
@@ -1993,12 +2047,10 @@ template <int C, class R, bool NT>
 static void launch_group_h(bool halo, bool ravg, int blocks, hipStream_t s, const GroupArgs &g) {
   const Params *p[kMaxGroup];
   for (int k = 0; k < kMaxGroup; ++k) p[k] = g.m[k < g.n ? k : 0].P;
-  if constexpr (C == 2 && sizeof(R) == 8) {
-    if (ravg) {  // several surface types, the type-0 averages in registers (no halo tiles)
-      hipLaunchKernelGGL((cells_atmos_group_kernel<C, R, NT, false, 0, true>), dim3(blocks),
-                         dim3(64 * atmos_waves<C>()), 0, s, g, p[0], p[1], p[2], p[3]);
-      return;
-    }
+  if (ravg) {  // several surface types, the type-0 averages in registers (no halo tiles)
+    hipLaunchKernelGGL((cells_atmos_group_kernel<C, R, NT, false, 0, true>), dim3(blocks),
+                       dim3(64 * atmos_waves<C>()), 0, s, g, p[0], p[1], p[2], p[3]);
+    return;
   }
   if constexpr (C == 2 && sizeof(R) == 8) {
     bool dense = halo;  // every member keeps per-cell records of the six fluxes
@@ -2038,13 +2090,13 @@ int launch_cells_group(GroupMember *members, int n, const LaunchConfig &lc, void
   if (total == 0) return 0;
   const int64_t kw = lc.wide ? atmos_waves<kWideCpl>() : lc.f32 ? atmos_waves<kF32Cpl>() : atmos_waves<2>();
   const int blocks = (int)std::max<int64_t>(1, (total + kw - 1) / kw);
-  if (lc.ravg && (lc.f32 || lc.halo > 0)) return (int)hipErrorInvalidValue;
+  if (lc.ravg && lc.halo > 0) return (int)hipErrorInvalidValue;
   if (lc.wide && !lc.f32) return (int)hipErrorInvalidValue;
   if (lc.wide) {
-    launch_wide_group(lc.nontemporal, lc.halo > 0, blocks, s, g);
+    launch_wide_group(lc.nontemporal, lc.halo > 0, lc.ravg, blocks, s, g);
   } else if (lc.f32) {
-    if (lc.nontemporal) launch_group_h<kF32Cpl, float, true>(lc.halo > 0, false, blocks, s, g);
-    else launch_group_h<kF32Cpl, float, false>(lc.halo > 0, false, blocks, s, g);
+    if (lc.nontemporal) launch_group_h<kF32Cpl, float, true>(lc.halo > 0, lc.ravg, blocks, s, g);
+    else launch_group_h<kF32Cpl, float, false>(lc.halo > 0, lc.ravg, blocks, s, g);
   } else {
     if (lc.nontemporal) launch_group_h<2, double, true>(lc.halo > 0, lc.ravg, blocks, s, g);
     else launch_group_h<2, double, false>(lc.halo > 0, lc.ravg, blocks, s, g);
@@ -2233,10 +2285,13 @@ int launch_fill(double *x, int64_t n, double value, bool f32, int64_t tpad, void
 
 #else  // FCX_KERNELS_WIDE_TU: the launchers of the F32Wide instantiations
 
-int launch_wide_fused(int variant, bool halo, bool nt, int blocks, hipStream_t s, const Params *dp,
+int launch_wide_fused(int variant, bool halo, bool ravg, bool nt, int blocks, hipStream_t s, const Params *dp,
                       const double *corr_m, const AtmosFused &af, int64_t lo, int64_t hi) {
+  if (ravg && halo) return (int)hipErrorInvalidValue;
 #define FCX_WIDE_ATM(VAR)                                                                            \
-  if (halo)                                                                                          \
+  if (ravg)  /* several types, the type-0 averages in registers */                                   \
+    launch_atm<kWideCpl, F32Wide, VAR, 0, true>(nt, blocks, s, dp, corr_m, af, lo, hi);              \
+  else if (halo)                                                                                     \
     launch_atm<kWideCpl, F32Wide, VAR, 1, false, false, true>(nt, blocks, s, dp, corr_m, af, lo, hi); \
   else                                                                                               \
     launch_atm<kWideCpl, F32Wide, VAR, 1, false>(nt, blocks, s, dp, corr_m, af, lo, hi);
@@ -2258,11 +2313,11 @@ void launch_wide_cells(int c, const Params *hp, const LaunchConfig &lc, int bloc
     launch_r<1, F32Wide>(hp, lc, blocks, s, dp, corr_m, lo, hi);
 }
 
-void launch_wide_group(bool nt, bool halo, int blocks, hipStream_t s, const GroupArgs &g) {
+void launch_wide_group(bool nt, bool halo, bool ravg, int blocks, hipStream_t s, const GroupArgs &g) {
   if (nt)
-    launch_group_h<kWideCpl, F32Wide, true>(halo, false, blocks, s, g);
+    launch_group_h<kWideCpl, F32Wide, true>(halo, ravg, blocks, s, g);
   else
-    launch_group_h<kWideCpl, F32Wide, false>(halo, false, blocks, s, g);
+    launch_group_h<kWideCpl, F32Wide, false>(halo, ravg, blocks, s, g);
 }
 #endif
 

@@ -404,6 +404,14 @@ MODULE fcx_c_api
       INTEGER(c_int32_t), INTENT(OUT) :: on
       INTEGER(c_int) :: fcx_f32_math
     END FUNCTION
+    ! after fcx_commit: 1 = the phase's exchange -> atmosphere accumulation rides in the flux launch
+    FUNCTION fcx_fused_accumulation(engine, phase, on) BIND(C, name='fcx_fused_accumulation')
+      IMPORT :: c_int, c_int32_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int), VALUE :: phase
+      INTEGER(c_int32_t), INTENT(OUT) :: on
+      INTEGER(c_int) :: fcx_fused_accumulation
+    END FUNCTION
     ! 1: the boundary-exchange signature agreement before every exchange (0: first of each)
     FUNCTION fcx_comm_verify(comm, every_exchange) BIND(C, name='fcx_comm_verify')
       IMPORT :: c_int, c_ptr

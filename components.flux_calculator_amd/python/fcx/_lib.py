@@ -100,6 +100,7 @@ SIGNATURES = [
     ("fcx_last_group_size", _I, [_P, _c.POINTER(_I32)]),
     ("fcx_atm_records", _I, [_P, _c.POINTER(_I32)]),
     ("fcx_f32_math", _I, [_P, _c.POINTER(_I32)]),
+    ("fcx_fused_accumulation", _I, [_P, _I, _c.POINTER(_I32)]),
     ("fcx_step_async", _I, [_P, _I, _I32]),
     ("fcx_upload_field", _I, [_P, _I, _I, _I]),
     ("fcx_comm_verify", _I, [_P, _I]),

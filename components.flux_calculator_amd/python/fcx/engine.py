@@ -317,6 +317,13 @@ class Engine:
         _lib.check(self.lib.fcx_f32_math(self.h, ctypes.byref(on)))
         return bool(on.value)
 
+    def fused_accumulation(self, phase=PHASE_ALL):
+        """True when the phase's exchange -> atmosphere accumulation rides inside the flux launch,
+        False when atmos_kernel runs it as a second pass (fcx_fused_accumulation)."""
+        on = ctypes.c_int32()
+        _lib.check(self.lib.fcx_fused_accumulation(self.h, int(phase), ctypes.byref(on)))
+        return bool(on.value)
+
     def close(self):
         if self.h is not None:
             self.lib.fcx_destroy(self.h)
@@ -330,7 +337,8 @@ class Engine:
 
 
 def run_group(engines, phase=PHASE_ALL, current_step_time=0):
-    """fcx_run of every engine, the fused T = 1 flux passes of the same shape as ONE launch
+    """fcx_run of every engine, the fused flux passes of the same shape (one surface type, or
+    several with the type-0 averages in registers, in any precision) as ONE launch
     (fcx_run_group): the same results as Engine.run of each."""
     if not engines:
         return

@@ -219,8 +219,10 @@ int fcx_upload(fcx_engine *e, int phase);   /* H2D of host-bound inputs of the p
 int fcx_run(fcx_engine *e, int phase, int32_t current_step_time); /* device compute  */
 int fcx_download(fcx_engine *e, int phase); /* D2H of host-bound outputs of the phase */
 /* fcx_run of several engines on one device (e.g. one per bottom-model variant), in the order
- * given: the flux passes of those whose phase is one fused T = 1 launch of the same shape on
- * the same stream go out as ONE launch (at most 4 engines; the others run as fcx_run), so a
+ * given: the flux passes of those whose phase is one fused launch of the same shape: one
+ * surface type, or several with the type-0 averages in registers, in any precision (engines of
+ * one precision and arithmetic merge with each other, single-type ones with single-type ones)
+ * on the same stream go out as ONE launch (at most 4 engines; the others run as fcx_run), so a
  * step pays the launch ramp and drain once.  Results are those of fcx_run of each, bit for
  * bit. */
 int fcx_run_group(fcx_engine *const *engines, int n_engines, int phase, int32_t current_step_time);
@@ -235,6 +237,11 @@ int fcx_atm_records(const fcx_engine *e, int32_t *on);
 /* 1 when the engine is an fp32 engine whose fluxes are computed in double (FCX_OPT_F32_MATH, by
  * the option or the environment's default), 0 otherwise; before fcx_commit: what it would apply */
 int fcx_f32_math(const fcx_engine *e, int32_t *on);
+/* after fcx_commit: 1 when the phase's exchange -> atmosphere accumulation rides inside the flux
+ * launch (no second pass over the fields), 0 when atmos_kernel runs it; FCX_E_STATE before commit,
+ * FCX_E_ARG for a phase outside 1..3 or a NULL pointer.  It may build the phase's plan (as the
+ * first fcx_run of the phase would) and changes nothing else */
+int fcx_fused_accumulation(fcx_engine *e, int phase, int32_t *on);
 /* the three above; with host-bound fields pipelined over cell chunks (FCX_OPT_PIPELINE_CHUNKS) */
 int fcx_step(fcx_engine *e, int phase, int32_t current_step_time);
 /* waits for the engine's stream; the caller's host arrays hold the downloaded outputs once it
@@ -485,7 +492,9 @@ enum fcx_option {
                                    consumed in double, unrounded (QSUR -> MEVA and momentum,
                                    MEVA (+ bias) -> HLAT, T_a * EF and the exchange-rate
                                    numerators formed once per cell, a type-0 average formed in
-                                   registers / LDS from the types' fluxes); a value read back
+                                   registers / LDS from the types' fluxes, with or without the
+                                   fused accumulation riding in the launch: its accumulators
+                                   are doubles either way); a value read back
                                    from an array is the stored float, widened (a per-call
                                    subroutine, a regridded field, an average that re-reads its
                                    fields).  Unchanged: the bias slice (rounded to float at
@@ -493,8 +502,9 @@ enum fcx_option {
                                    pass (do_regridding in REAL(4), the accumulation kernel,
                                    fix-up, remaps, record packing, constant fills) and the
                                    fused accumulation's products w * (double)x32 of the
-                                   float-rounded flux, so an atmosphere output stays the
-                                   sequential fp64 sum of the engine's own stored fluxes,
+                                   float-rounded flux (several surface types: of the
+                                   float-rounded type-0 average), so an atmosphere output stays
+                                   the sequential fp64 sum of the engine's own stored values,
                                    rounded once.  No flux is computed in float with it on.
                                    Accepted and without effect on an fp64 engine.  Applied at
                                    fcx_commit (FCX_E_STATE afterwards); other values are
