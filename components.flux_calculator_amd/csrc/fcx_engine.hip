@@ -151,6 +151,15 @@ struct Buffer : HostMirror {
   // Cleared when a consumer outside the flux pass needs the array (then filled: kind 2).
   bool uniform = false;
   bool filled = false;
+  // fcx_bind_received: the exchange-grid array of a received field.  Like a constant's it has let
+  // go of the caller's array and lives in the engine's pools, never transferred; its values come
+  // from the gather launch of its declaration (recv: index into fcx_engine::received).
+  int recv = -1;
+  // ... and the model-grid array the host receives into: an ordinary input mirror of n_src
+  // elements that every transport takes, bound to no slot
+  bool source = false;
+  // an input the engine keeps in an array of its own that no transport moves
+  bool engine_input() const { return constant || recv >= 0; }
 };
 
 // A field of (s, g, var) summed to another grid in `phase`: an atmosphere output (the
@@ -447,6 +456,29 @@ struct fcx_engine {
   bool lib_spans = true;
   std::vector<Span> spans;
   std::vector<char> written;  // per buffer: some plan writes it (never part of an upload run)
+  // Receive side (fcx_add_receive_map / fcx_bind_received): model grid -> exchange grid maps, each
+  // classified once at commit -- injection (at most one link per exchange cell: idx, and cellw
+  // where some weight is not 1.0) or general (CSR by exchange cell in link order)
+  struct ReceiveMap {
+    int grid = 1;
+    int64_t n_src = 0, n_links = 0;
+    std::vector<int32_t> src, dst;
+    std::vector<double> w;
+    bool injection = false, weighted = false;
+    DevArray<int32_t> d_idx;
+    DevArray<double> d_cellw;
+    Csr csr;
+    int64_t map_bytes = 0;  // what one gather launch reads of the map
+  };
+  std::vector<ReceiveMap> rmaps;
+  // one declared buffer: gathered through `map` at the start of `phase` from buffer `src`
+  struct Received {
+    int map, phase, src, dst;
+    int s, g, var;             // the slot of the first declaration (messages)
+    std::string conflict;      // a declaration of a slot on another grid than the map's, or a later
+                               // declaration of the buffer that disagrees with the first
+  };
+  std::vector<Received> received;
 
   fcx_engine() {
     for (auto &a : slot)
@@ -721,6 +753,150 @@ extern "C" int fcx_constant_info(const fcx_engine *e, int s, int g, int var, int
 
 static const char *grid_name(int g) { return g == 1 ? "t" : g == 2 ? "u" : "v"; }
 
+extern "C" int fcx_add_receive_map(fcx_engine *e, int grid, int64_t n_src, int64_t n_links, const int32_t *src,
+                                   const int32_t *dst, const double *w, int32_t *map_id) {
+  if (!e || !map_id) return fail(FCX_E_ARG, "NULL argument");
+  if (e->committed) return fail(FCX_E_STATE, "engine already committed");
+  if (grid < 1 || grid > 3) return fail(FCX_E_ARG, "receive map: grid %d outside 1..3", grid);
+  if (n_src < 1 || n_src > INT32_MAX) return fail(FCX_E_ARG, "receive map: n_src %lld outside 1..2^31-1", (long long)n_src);
+  if (n_links < 0 || n_links > INT32_MAX || (n_links > 0 && (!src || !dst || !w)))
+    return fail(FCX_E_ARG, "receive map: bad link arrays");
+  const int64_t n_dst = e->n[grid - 1];
+  for (int64_t k = 0; k < n_links; ++k) {
+    if (src[k] < 0 || src[k] >= n_src || dst[k] < 0 || dst[k] >= n_dst)
+      return fail(FCX_E_ARG, "receive map link %lld (%d -> %d) outside the %lld model cells / %lld %s-grid cells",
+                  (long long)k, src[k], dst[k], (long long)n_src, (long long)n_dst, grid_name(grid));
+    if (!std::isfinite(w[k])) return fail(FCX_E_ARG, "receive map link %lld: weight is not finite", (long long)k);
+  }
+  fcx_engine::ReceiveMap m;
+  m.grid = grid;
+  m.n_src = n_src;
+  m.n_links = n_links;
+  m.src.assign(src, src + n_links);
+  m.dst.assign(dst, dst + n_links);
+  m.w.assign(w, w + n_links);
+  *map_id = (int32_t)e->rmaps.size();
+  e->rmaps.push_back(std::move(m));
+  return FCX_OK;
+}
+
+extern "C" int fcx_bind_received(fcx_engine *e, int32_t map_id, int phase, int s, int g, int var, double *src, int64_t n,
+                                 int flags) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (e->committed) return fail(FCX_E_STATE, "engine already committed");
+  if (s < 0 || s > kMaxTypes || g < 1 || g > 3 || var < 1 || var > kNumVars)
+    return fail(FCX_E_ARG, "slot (%d,%d,%d) out of range", s, g, var);
+  if (map_id < 0 || (size_t)map_id >= e->rmaps.size()) return fail(FCX_E_ARG, "receive map %d unknown", (int)map_id);
+  if (phase != FCX_PHASE_EARLY && phase != FCX_PHASE_NORMAL)
+    return fail(FCX_E_ARG, "%s(%d,%s): a received field belongs to the early (1) or the normal (2) phase, got %d",
+                kVarNames[var0(var)], s, grid_name(g), phase);
+  const fcx_engine::ReceiveMap &m = e->rmaps[(size_t)map_id];
+  if (!src) return fail(FCX_E_ARG, "%s(%d,%s): the source array is NULL", kVarNames[var0(var)], s, grid_name(g));
+  if (n < m.n_src)
+    return fail(FCX_E_ARG, "%s(%d,%s): source array of %lld cells shorter than the map's n_src %lld", kVarNames[var0(var)],
+                s, grid_name(g), (long long)n, (long long)m.n_src);
+  const bool on_dev = flags & FCX_MEM_DEVICE;
+  // the source: an input mirror of its own length, shared by every declaration that names it
+  int sb;
+  auto it = e->by_ptr.find(src);
+  if (it == e->by_ptr.end()) {
+    Buffer bf;
+    bf.n = m.n_src;
+    bf.source = true;
+    if (on_dev) {
+      bf.dev = src;
+      bf.external = true;
+    } else {
+      bf.host = src;
+    }
+    sb = (int)e->bufs.size();
+    e->bufs.push_back(bf);
+    e->by_ptr[src] = sb;
+  } else {
+    sb = it->second;
+    if (!e->bufs[(size_t)sb].source)
+      return fail(FCX_E_ARG, "%s(%d,%s): the source array is bound as an exchange-grid field", kVarNames[var0(var)], s,
+                  grid_name(g));
+    if (e->bufs[(size_t)sb].external != on_dev) return fail(FCX_E_ARG, "pointer bound both as host and as device memory");
+    if (e->bufs[(size_t)sb].n != m.n_src)
+      return fail(FCX_E_ARG, "%s(%d,%s): the source array serves maps of %lld and of %lld model cells", kVarNames[var0(var)],
+                  s, grid_name(g), (long long)e->bufs[(size_t)sb].n, (long long)m.n_src);
+  }
+  int b = e->buf(s, g, var);
+  if (b >= 0 && e->bufs[(size_t)b].source)
+    return fail(FCX_E_ARG, "%s(%d,%s) is bound to a source array", kVarNames[var0(var)], s, grid_name(g));
+  if (b < 0) {  // no caller array at all: an own field
+    Buffer bf;
+    bf.n = e->n[g - 1];
+    b = (int)e->bufs.size();
+    e->bufs.push_back(bf);
+    e->slot[s][g - 1][var0(var)] = b;
+    e->allocated[s][g - 1][var0(var)] = true;
+  }
+  // a bound array: the buffer -- and with it every slot bound to that address -- lets go of it
+  Buffer &bf = e->bufs[(size_t)b];
+  if (bf.host || bf.external) e->by_ptr.erase(bf.external ? bf.dev : bf.host);
+  bf.host = nullptr;
+  if (bf.external) bf.dev = nullptr;
+  bf.external = false;
+  bf.n = std::max(bf.n, e->n[g - 1]);
+  char grid_msg[200] = "";
+  if (m.grid != g)  // (a named error of fcx_plan_check / fcx_commit, with the other declaration errors)
+    snprintf(grid_msg, sizeof grid_msg, "received field %s(%d,%s): its map gathers to the %s grid", kVarNames[var0(var)], s,
+             grid_name(g), grid_name(m.grid));
+  if (bf.recv >= 0) {  // declared before: the declarations must agree (fcx_plan_check / fcx_commit)
+    fcx_engine::Received &r = e->received[(size_t)bf.recv];
+    if ((r.map != map_id || r.phase != phase || r.src != sb) && r.conflict.empty()) {
+      char msg[200];
+      snprintf(msg, sizeof msg, "received field %s(%d,%s) and its alias %s(%d,%s) are declared with different maps, phases or sources",
+               kVarNames[var0(r.var)], r.s, grid_name(r.g), kVarNames[var0(var)], s, grid_name(g));
+      r.conflict = msg;
+    }
+    if (r.conflict.empty()) r.conflict = grid_msg;
+    return FCX_OK;
+  }
+  bf.recv = (int)e->received.size();
+  e->received.push_back(fcx_engine::Received{(int)map_id, phase, sb, b, s, g, var, grid_msg});
+  return FCX_OK;
+}
+
+extern "C" int fcx_received_info(const fcx_engine *e, int s, int g, int var, int32_t *kind, int32_t *map_id) {
+  if (!e || !kind || !map_id) return fail(FCX_E_ARG, "NULL argument");
+  if (!e->committed) return fail(FCX_E_STATE, "fcx_commit has not been called");
+  if (s < 0 || s > kMaxTypes || g < 1 || g > 3 || var < 1 || var > kNumVars)
+    return fail(FCX_E_ARG, "slot (%d,%d,%d) out of range", s, g, var);
+  const int b = e->buf(s, g, var);
+  *kind = 0;
+  *map_id = -1;
+  if (b >= 0 && e->bufs[(size_t)b].recv >= 0) {
+    *kind = 1;
+    *map_id = e->received[(size_t)e->bufs[(size_t)b].recv].map;
+  }
+  return FCX_OK;
+}
+
+// The declarations of the received fields against each other and against the slots: named
+// FCX_E_STATE errors of fcx_plan_check / fcx_commit.  (A received buffer some plan would write is
+// found where a written constant is: build_plan, constants_check.)
+static int received_check(const fcx_engine *e) {
+  for (const auto &r : e->received) {
+    const Buffer &bf = e->bufs[(size_t)r.dst];
+    if (!r.conflict.empty()) return fail(FCX_E_STATE, "%s", r.conflict.c_str());
+    if (bf.constant)
+      return fail(FCX_E_STATE, "received field %s(%d,%s) is also a namelist constant", kVarNames[var0(r.var)], r.s,
+                  grid_name(r.g));
+    for (int s = 0; s <= kMaxTypes; ++s)
+      for (int g = 1; g <= 3; ++g)
+        for (int v = 1; v <= kNumVars; ++v)
+          // (an alias on another grid -- the u / v grids that ARE the t grid -- has that grid's size)
+          if (e->slot[s][g - 1][v - 1] == r.dst && e->n[e->rmaps[(size_t)r.map].grid - 1] != e->n[g - 1])
+            return fail(FCX_E_STATE, "received field %s(%d,%s): its map gathers to the %lld cells of the %s grid",
+                        kVarNames[v - 1], s, grid_name(g), (long long)e->n[e->rmaps[(size_t)r.map].grid - 1],
+                        grid_name(e->rmaps[(size_t)r.map].grid));
+  }
+  return FCX_OK;
+}
+
 extern "C" int fcx_set_output_use(fcx_engine *e, int s, int g, int var, int use) {
   if (!e) return fail(FCX_E_ARG, "NULL engine");
   if (e->committed) return fail(FCX_E_STATE, "engine already committed");
@@ -763,6 +939,9 @@ static int settle_output_use(fcx_engine *e) {
         Buffer &bf = e->bufs[(size_t)b];
         if (bf.constant)
           return fail(FCX_E_STATE, "output use of the constant field %s(%d,%s): a namelist constant is an input",
+                      kVarNames[v - 1], s, grid_name(g));
+        if (bf.recv >= 0)
+          return fail(FCX_E_STATE, "output use of the received field %s(%d,%s): a received field is an input",
                       kVarNames[v - 1], s, grid_name(g));
         bf.use = (int8_t)(bf.use == FCX_OUT_HOST ? use : std::min<int>(bf.use, use));
       }
@@ -1140,7 +1319,7 @@ static int ravg_slot(const fcx_engine *e, const Params &P, uint32_t stages, int 
 // load FARE(s) and, for the TSUR slot, TSUR(s) under the same conditions as the fp64 ones.
 // the mirror of a constant, filled once (stream-ordered before whatever reads it)
 static int fill_constant(fcx_engine *e, Buffer &bf) {
-  if (bf.filled || bf.n <= 0 || !bf.dev) return FCX_OK;
+  if (bf.filled || bf.n <= 0 || !bf.dev || !bf.constant) return FCX_OK;  // (a received field: its gather fills it)
   const int r = launch_fill(bf.dev, bf.n, bf.cval, e->f32, e->tpad, e->stream);
   if (r) return fail(FCX_E_HIP, "constant fill launch: %s", hipGetErrorString((hipError_t)r));
   bf.filled = true;
@@ -1418,16 +1597,21 @@ static int build_plan(fcx_engine *e, uint32_t stages, int avg_phases, Plan &pl) 
     if (b < 0) return nullptr;
     if (e->plan_dry && unbind && std::strcmp(unbind, kVarNames[var0(var)]) == 0) return nullptr;
     // a constant is read from its filled mirror: never uploaded, staged, spanned or mapped
-    (e->bufs[(size_t)b].constant ? const_reads : reads).insert(b);
+    // (nor is a received field: its gather launch writes the engine's array)
+    (e->bufs[(size_t)b].engine_input() ? const_reads : reads).insert(b);
     return dev_of(b);
   };
   auto out = [&](int s, int g, int var) -> double * {
     const int b = e->buf(s, g, var);
     if (b < 0) return nullptr;
-    if (e->bufs[(size_t)b].constant && const_written.empty()) {
+    if (e->bufs[(size_t)b].engine_input() && const_written.empty()) {
       char msg[160];
-      snprintf(msg, sizeof msg, "constant field %s(%d,%s) would be written (stages 0x%x): a namelist constant is an input",
-               kVarNames[var0(var)], s, g == 1 ? "t" : g == 2 ? "u" : "v", (unsigned)stages);
+      if (e->bufs[(size_t)b].constant)
+        snprintf(msg, sizeof msg, "constant field %s(%d,%s) would be written (stages 0x%x): a namelist constant is an input",
+                 kVarNames[var0(var)], s, g == 1 ? "t" : g == 2 ? "u" : "v", (unsigned)stages);
+      else
+        snprintf(msg, sizeof msg, "received field %s(%d,%s) would be written (stages 0x%x): a received field is an input",
+                 kVarNames[var0(var)], s, g == 1 ? "t" : g == 2 ? "u" : "v", (unsigned)stages);
       const_written = msg;
     }
     writes.insert(b);
@@ -1614,7 +1798,7 @@ static int build_plan(fcx_engine *e, uint32_t stages, int avg_phases, Plan &pl) 
         // values produced in this launch are re-read by the same thread (in order)
         ae.x[s - 1] = dev_of(e->buf(s, g, var));
         if (!writes.count(e->buf(s, g, var)))
-          (e->bufs[(size_t)e->buf(s, g, var)].constant ? const_reads : reads).insert(e->buf(s, g, var));
+          (e->bufs[(size_t)e->buf(s, g, var)].engine_input() ? const_reads : reads).insert(e->buf(s, g, var));
         ae.fare[s - 1] = in(s, g, FCX_FARE);
       }
       n_max = std::max(n_max, e->n[g - 1]);
@@ -1688,7 +1872,7 @@ static int staged_sequence(int phase, std::vector<std::pair<uint32_t, int>> &seq
 static void decide_uniform(fcx_engine *e) {
   static const int kIn[] = {FCX_TSUR, FCX_FICE, FCX_PSUR, FCX_PATM, FCX_QATM, FCX_TATM, FCX_UATM,
                             FCX_VATM, FCX_AMOI, FCX_CMOI, FCX_CHEA, FCX_AMOM, FCX_CMOM};
-  for (auto &bf : e->bufs) bf.uniform = bf.constant && e->const_uniform;
+  for (auto &bf : e->bufs) bf.uniform = bf.constant && bf.recv < 0 && e->const_uniform;
   auto array = [&](int s, int g, int v) {
     const int b = e->buf(s, g, v);
     if (b >= 0) e->bufs[(size_t)b].uniform = false;
@@ -1712,6 +1896,10 @@ static int constants_check(const fcx_engine *e) {
     const int b = e->buf(s, g, var);
     return b >= 0 && e->bufs[(size_t)b].constant;
   };
+  auto is_recv = [&](int s, int g, int var) {
+    const int b = e->buf(s, g, var);
+    return b >= 0 && e->bufs[(size_t)b].recv >= 0;
+  };
   auto gname = [](int g) { return g == 1 ? "t" : g == 2 ? "u" : "v"; };
   static const struct {
     int flux, g, var;
@@ -1725,12 +1913,24 @@ static int constants_check(const fcx_engine *e) {
       if (e->method[c.flux][s - 1] == FCX_COPY && is_const(s, c.g, c.var))
         return fail(FCX_E_STATE, "constant field %s(%d,%s) is the target of a 'copy' method: a namelist constant is an input",
                     kVarNames[var0(c.var)], s, gname(c.g));
+  for (int s = 1; s <= e->T; ++s)
+    for (auto &c : kCopy)
+      if (e->method[c.flux][s - 1] == FCX_COPY && is_recv(s, c.g, c.var))
+        return fail(FCX_E_STATE, "received field %s(%d,%s) is the target of a 'copy' method: a received field is an input",
+                    kVarNames[var0(c.var)], s, gname(c.g));
   for (int s = 0; s <= kMaxTypes; ++s)
     for (int g = 1; g <= 3; ++g)
       for (int v = 1; v <= kNumVars; ++v)
         for (int k = 0; k < 3; ++k)
           if (((e->put_to[s][g - 1][v - 1] >> k) & 1) && k + 1 != g && is_const(s, k + 1, v))
             return fail(FCX_E_STATE, "constant field %s(%d,%s) is a regridding destination: a namelist constant is an input",
+                        kVarNames[v - 1], s, gname(k + 1));
+  for (int s = 0; s <= kMaxTypes; ++s)
+    for (int g = 1; g <= 3; ++g)
+      for (int v = 1; v <= kNumVars; ++v)
+        for (int k = 0; k < 3; ++k)
+          if (((e->put_to[s][g - 1][v - 1] >> k) & 1) && k + 1 != g && is_recv(s, k + 1, v))
+            return fail(FCX_E_STATE, "received field %s(%d,%s) is a regridding destination: a received field is an input",
                         kVarNames[v - 1], s, gname(k + 1));
   return FCX_OK;
 }
@@ -1740,6 +1940,7 @@ extern "C" int fcx_plan_check(fcx_engine *e) {
   if (!e) return fail(FCX_E_ARG, "NULL engine");
   if (e->committed) return fail(FCX_E_STATE, "fcx_plan_check runs before fcx_commit");
   if (int r = validate(e)) return r;
+  if (int r = received_check(e)) return r;
   if (int r = settle_output_use(e)) return r;
   decide_uniform(e);
   return plan_check_all(e);
@@ -2171,15 +2372,23 @@ static int alloc_tiled(fcx_engine *e) {
     const int b = e->buf(0, a.second.first, a.second.second);
     if (b >= 0 && cls[b] == kCold) cls[b] = kWrite;
   }
-  int64_t n_max = 0;
+  // (the model-grid sources of received fields, fcx_bind_received, have lengths of their own:
+  // they get pools of the same tile stride with only as many tile rows as the longest of them,
+  // so that their page-locked staging image is about their own size)
+  int64_t n_max = 0, n_src_max = 0;
   int count[3] = {0, 0, 0};
   for (size_t b = 0; b < e->bufs.size(); ++b) {
+    if (e->bufs[b].source) {
+      n_src_max = std::max(n_src_max, e->bufs[b].n);
+      continue;
+    }
     n_max = std::max(n_max, e->bufs[b].n);
     ++count[cls[b]];
   }
   const int64_t S = std::max(1, std::max(count[kRead], count[kWrite]));
   const int64_t tiles = std::max<int64_t>(1, (n_max + kLayoutTile - 1) / kLayoutTile);
   const size_t bytes = (size_t)tiles * S * kLayoutTile * e->esize;
+  const size_t src_bytes = (size_t)std::max<int64_t>(1, (n_src_max + kLayoutTile - 1) / kLayoutTile) * S * kLayoutTile * e->esize;
   e->tiled_bytes = bytes;
   // pool and slot of every buffer: read pool, write pool, then the cold ones S to a pool
   std::vector<std::pair<int, int>> at(e->bufs.size());
@@ -2189,9 +2398,19 @@ static int alloc_tiled(fcx_engine *e) {
   std::vector<size_t> order;
   for (int pass = 0; pass < 2; ++pass)
     for (size_t b = 0; b < e->bufs.size(); ++b)
-      if ((e->bufs[b].constant || e->bufs[b].use != FCX_OUT_HOST) == (pass == 1)) order.push_back(b);
+      if ((e->bufs[b].engine_input() || e->bufs[b].use != FCX_OUT_HOST) == (pass == 1)) order.push_back(b);
+  std::vector<char> src_pool;  // per pool: holds sources only
+  int last_src_pool = -1, src_fill = 0;
   for (size_t b : order) {
     const int c = cls[b];
+    if (e->bufs[b].source) {
+      if (e->bufs[b].external) continue;  // (the caller's device memory)
+      if (last_src_pool < 0 || src_fill == S) last_src_pool = npools++, src_fill = 0;
+      at[b] = {last_src_pool, src_fill++};
+      src_pool.resize((size_t)npools, 0);
+      src_pool[(size_t)last_src_pool] = 1;
+      continue;
+    }
     if (c != kCold) {
       if (pool_of[c] < 0) pool_of[c] = npools++;
       at[b] = {pool_of[c], fill[c]++};
@@ -2200,16 +2419,18 @@ static int alloc_tiled(fcx_engine *e) {
       at[b] = {cold_pool, fill[kCold]++};
     }
   }
+  src_pool.resize((size_t)npools, 0);
   for (int k = 0; k < npools; ++k) {
     DevArray<void> p;
-    hipError_t err = p.alloc(bytes);
+    hipError_t err = p.alloc(src_pool[(size_t)k] ? src_bytes : bytes);
     if (err != hipSuccess)
       return fail(FCX_E_NOMEM, "hipMalloc(%zu) for the tiled field mirrors: %s", bytes, hipGetErrorString(err));
     e->tiled_pools.push_back(std::move(p));
   }
   for (size_t b = 0; b < e->bufs.size(); ++b)
-    e->bufs[b].dev = reinterpret_cast<double *>((char *)e->tiled_pools[at[b].first].p +
-                                                (size_t)at[b].second * kLayoutTile * e->esize);
+    if (!e->bufs[b].external)  // (a received field's source in the caller's device memory stays there)
+      e->bufs[b].dev = reinterpret_cast<double *>((char *)e->tiled_pools[at[b].first].p +
+                                                  (size_t)at[b].second * kLayoutTile * e->esize);
   e->tpad = (S - 1) * kLayoutTile;
   return FCX_OK;
 }
@@ -2300,7 +2521,7 @@ static void stage_setup(fcx_engine *e) {
   const size_t es = e->esize;
   std::vector<StagePool> cand;
   for (auto &p : e->tiled_pools)
-    cand.push_back(StagePool{(char *)p.p, nullptr, e->tiled_bytes, true, (size_t)kLayoutTile * es,
+    cand.push_back(StagePool{(char *)p.p, nullptr, p.bytes, true, (size_t)kLayoutTile * es,
                              (size_t)(kLayoutTile + e->tpad) * es});
   if (e->pool) cand.push_back(StagePool{(char *)e->pool.p, nullptr, e->pool_staged_bytes, false, 0, 0});
   int atm_cand = -1;  // records: the pool the downloads read does not exist yet (atm_unpack)
@@ -2704,7 +2925,8 @@ static int commit_transports(fcx_engine *e) {
 // the field mirrors: tile-blocked pools, or one pooled allocation
 static int commit_field_pools(fcx_engine *e) {
   bool any_external = false;
-  for (auto &bf : e->bufs) any_external = any_external || bf.external;
+  // (a source in the caller's device memory is read by the gather alone, as a contiguous array)
+  for (auto &bf : e->bufs) any_external = any_external || (bf.external && !(bf.source && !bf.host));
   if (e->tiled_opt && !any_external && !e->bufs.empty()) {
     if (int r = alloc_tiled(e)) return r;
   } else {
@@ -2713,12 +2935,13 @@ static int commit_field_pools(fcx_engine *e) {
   // plain layout: one pooled allocation for all host-bound mirrors, 256-B aligned sub-buffers
   size_t total = 0;
   std::vector<size_t> off(e->bufs.size(), 0);
-  // (the outputs kept on the device, fcx_set_output_use, behind everything else: the pool's
-  // page-locked staging image ends where they begin -- they have no place in the arena)
+  // (the outputs kept on the device, fcx_set_output_use, and the received fields' exchange-grid
+  // arrays behind everything else: the pool's page-locked staging image ends where they begin
+  // -- they have no place in the arena)
   size_t staged = 0;
   for (int pass = 0; pass < 2 && e->tiled_pools.empty(); ++pass) {
     for (size_t b = 0; b < e->bufs.size(); ++b) {
-      if (e->bufs[b].external || (e->bufs[b].use != FCX_OUT_HOST) != (pass == 1)) continue;
+      if (e->bufs[b].external || (e->bufs[b].use != FCX_OUT_HOST || e->bufs[b].recv >= 0) != (pass == 1)) continue;
       off[b] = total;
       total += ((size_t)e->bufs[b].n * e->esize + 255) / 256 * 256;
     }
@@ -2747,6 +2970,97 @@ static int commit_constants(fcx_engine *e) {
     if (int r = fill_constant(e, bf)) return r;
   }
   if (any_constant) HIP_TRY(hipStreamSynchronize(e->stream));
+  return FCX_OK;
+}
+
+// The receive maps, each classified once.  Injection form: no exchange cell has two links --
+// one source index per exchange cell (-1: no link; padded with -1 to a whole 16-B vector) and a
+// weight per cell only where some weight is not exactly 1.0.  General form otherwise: CSR by
+// exchange cell in stable link order.  Maps no declaration uses stay on the host.
+static int commit_received(fcx_engine *e) {
+  std::vector<char> used(e->rmaps.size(), 0);
+  for (const auto &r : e->received) used[(size_t)r.map] = 1;
+  for (size_t i = 0; i < e->rmaps.size(); ++i) {
+    fcx_engine::ReceiveMap &m = e->rmaps[i];
+    if (!used[i]) continue;
+    const int64_t n = e->n[m.grid - 1];
+    std::vector<int32_t> idx((size_t)((n + 3) / 4 * 4 + 4), -1);
+    std::vector<double> cw((size_t)std::max<int64_t>(n, 1), 1.0);
+    m.injection = true;
+    m.weighted = false;
+    for (int64_t k = 0; k < m.n_links && m.injection; ++k) {
+      const size_t d = (size_t)m.dst[(size_t)k];
+      if (idx[d] >= 0) m.injection = false;
+      idx[d] = m.src[(size_t)k];
+      cw[d] = m.w[(size_t)k];
+      m.weighted = m.weighted || m.w[(size_t)k] != 1.0;
+    }
+    if (m.injection) {
+      if (int r = m.d_idx.upload(idx)) return r;
+      if (m.weighted)
+        if (int r = m.d_cellw.upload(cw)) return r;
+      m.map_bytes = n * 4 + (m.weighted ? n * 8 : 0);
+    } else {
+      m.csr.build(n, m.n_links, m.src.data(), m.dst.data(), m.w.data(), 0);
+      if (int r = m.csr.upload(false)) return r;
+      m.map_bytes = (n + 1) * 4 + m.n_links * 12;
+    }
+  }
+  return FCX_OK;
+}
+
+// the sources the host receives into before `phase` (each once)
+static std::vector<int> received_sources(const fcx_engine *e, int phase) {
+  std::vector<int> ids;
+  for (const auto &r : e->received)
+    if ((r.phase & phase) && std::find(ids.begin(), ids.end(), r.src) == ids.end()) ids.push_back(r.src);
+  return ids;
+}
+
+// The gather launches of `phase`, on the engine stream: per map the phase's received fields, at
+// most kMaxReceiveFields per launch, in declaration order.  *launch_bytes (no launch is made
+// with it): the algorithmic bytes of those launches -- the map once per launch, n_src elements
+// read and grid_size elements written per field.
+static int run_gathers(fcx_engine *e, int phase, int64_t *launch_bytes = nullptr) {
+  for (size_t mi = 0; mi < e->rmaps.size(); ++mi) {
+    const fcx_engine::ReceiveMap &m = e->rmaps[mi];
+    ReceiveArgs a{};
+    a.n = e->n[m.grid - 1];
+    a.tpad = e->tpad;
+    a.f32 = e->f32 ? 1 : 0;
+    if (m.injection) {
+      a.idx = m.d_idx;
+      a.w = m.weighted ? m.d_cellw.p : nullptr;
+    } else {
+      a.row_ptr = m.csr.d_row;
+      a.col = m.csr.d_col;
+      a.w = m.csr.d_w;
+    }
+    auto flush = [&]() -> int {
+      if (!a.nf) return FCX_OK;
+      if (launch_bytes) {
+        *launch_bytes += m.map_bytes + (int64_t)a.nf * (m.n_src + a.n) * (int64_t)e->esize;
+      } else {
+        const int r = launch_receive(a, e->stream);
+        if (r) return fail(FCX_E_HIP, "receive gather launch: %s", hipGetErrorString((hipError_t)r));
+      }
+      a.nf = 0;
+      a.src_plain = 0;
+      return FCX_OK;
+    };
+    for (const auto &r : e->received) {
+      if (r.map != (int)mi || !(r.phase & phase)) continue;
+      const Buffer &sb = e->bufs[(size_t)r.src];
+      // (sources outside the engine's pools -- the caller's device memory, a span, an array used
+      // in place -- are contiguous; with them the pools are not tiled, but for device memory)
+      if (sb.external) a.src_plain |= 1u << a.nf;
+      a.src[a.nf] = sb.dev;
+      a.dst[a.nf] = e->bufs[(size_t)r.dst].dev;
+      if (++a.nf == kMaxReceiveFields)
+        if (int rc = flush()) return rc;
+    }
+    if (int rc = flush()) return rc;
+  }
   return FCX_OK;
 }
 
@@ -2930,6 +3244,8 @@ static int commit_staging(fcx_engine *e) {
       for (const std::vector<int> *ids : {&pl->reads, &pl->writes})
         for (int b : *ids)
           if (e->bufs[(size_t)b].st.sp >= 0) eager[(size_t)e->bufs[(size_t)b].st.sp] = 1;
+      for (int b : received_sources(e, FCX_PHASE_ALL))
+        if (e->bufs[(size_t)b].st.sp >= 0) eager[(size_t)e->bufs[(size_t)b].st.sp] = 1;
     } else {
       std::fill(eager.begin(), eager.end(), 1);
     }
@@ -2945,15 +3261,16 @@ extern "C" int fcx_commit(fcx_engine *e) {
   if (!e) return fail(FCX_E_ARG, "NULL engine");
   if (e->committed) return FCX_OK;
   if (int r = validate(e)) return r;
+  if (int r = received_check(e)) return r;
   if (int r = settle_output_use(e)) return r;
   decide_uniform(e);
-  // a constant some plan would write, or a declared output none writes, is an error here, not
+  // a constant or a received field some plan would write, or a declared output none writes, is an error here, not
   // at that plan's first run
-  if (e->any_out_use || std::any_of(e->bufs.begin(), e->bufs.end(), [](const Buffer &bf) { return bf.constant; }))
+  if (e->any_out_use || std::any_of(e->bufs.begin(), e->bufs.end(), [](const Buffer &bf) { return bf.engine_input(); }))
     if (int r = plan_check_all(e, true)) return r;
   decide_output_keep(e);
   if (int r = gpu_init(e)) return r;
-  for (auto step : {commit_output_use, commit_transports, commit_field_pools, commit_constants, commit_corrections, commit_maps,
+  for (auto step : {commit_output_use, commit_transports, commit_field_pools, commit_constants, commit_received, commit_corrections, commit_maps,
                     commit_atmos_outputs, commit_shared_slots, commit_remaps, commit_staging})
     if (int r = step(e)) return r;
   return FCX_OK;
@@ -3277,9 +3594,10 @@ extern "C" int fcx_upload_field(fcx_engine *e, int s, int g, int var) {
   if (!e->committed) return fail(FCX_E_STATE, "fcx_commit has not been called");
   if (s < 0 || s > kMaxTypes || g < 1 || g > 3 || var < 1 || var > kNumVars)
     return fail(FCX_E_ARG, "field (%d, %d, %d) outside the data model", s, g, var);
-  const int b = e->buf(s, g, var);
+  int b = e->buf(s, g, var);
   if (b < 0) return fail(FCX_E_ARG, "local_field(%d,%d)%%var(%s) is not bound", s, g, kVarNames[var - 1]);
   if (e->bufs[(size_t)b].constant) return FCX_OK;  // nothing to hand over: the engine filled it at commit
+  if (e->bufs[(size_t)b].recv >= 0) b = e->received[(size_t)e->bufs[(size_t)b].recv].src;  // a received field: its source
   if (e->bufs[(size_t)b].use != FCX_OUT_HOST) return FCX_OK;  // an output kept on the device: no host array to hand over
   if (e->field_sent.size() != e->bufs.size()) e->field_sent.assign(e->bufs.size(), 0);
   if (e->field_sent[(size_t)b]) return FCX_OK;  // an alias of a field already handed over
@@ -3302,7 +3620,20 @@ extern "C" int fcx_upload(fcx_engine *e, int phase) {
   Plan *pl;
   if (int r = get_plan(e, phase_stages(phase), phase, &pl)) return r;
   if (int r = plan_stale_check(e, pl)) return r;
-  return copy_bufs(e, pl->reads, true);
+  if (e->received.empty()) return copy_bufs(e, pl->reads, true);
+  std::vector<int> ids = pl->reads;  // ... and the sources of the phase's received fields
+  for (int b : received_sources(e, phase)) ids.push_back(b);
+  return copy_bufs(e, ids, true);
+}
+
+// upload plus gather alone, for hosts of the per-call face: fcx_calc_* and fcx_do_regridding read
+// the received fields' device arrays as last gathered
+extern "C" int fcx_receive(fcx_engine *e, int phase) {
+  if (int r = check(e)) return r;
+  if (phase < 1 || phase > 3) return fail(FCX_E_ARG, "phase %d unknown", phase);
+  if (int r = copy_bufs(e, received_sources(e, phase), true)) return r;
+  fields_taken(e);
+  return run_gathers(e, phase);
 }
 
 extern "C" int fcx_download(fcx_engine *e, int phase) {
@@ -3511,6 +3842,7 @@ extern "C" int fcx_run(fcx_engine *e, int phase, int32_t t) {
   e->rec_plan = nullptr;
   e->group_members = 0;
   fields_taken(e);
+  if (int r = run_gathers(e, phase)) return r;  // the received fields, before any regridding or flux pass
   if (!e->any_regrid) {
     Plan *pl;
     if (int r = get_plan(e, phase_stages(phase), phase, &pl)) return r;
@@ -3600,6 +3932,8 @@ extern "C" int fcx_run_group(fcx_engine *const *es, int n, int phase, int32_t t)
   // every engine's tail (fix-up, accumulation, boundary exchange of an attached communicator,
   // remaps) runs in LIST order below, whichever engines could join: group eligibility is
   // rank-local (map, grid cap, halo), the order of the per-engine all-reduces must not be
+  for (const auto &m : mem)  // the members' received fields, before the merged launch (one stream)
+    if (int r = run_gathers(m.e, phase)) return r;
   if (!mem.empty())
     if (int r = launch_group(mem.data(), (int)mem.size())) return r;
   for (int i = 0; i < n; ++i) {
@@ -3709,6 +4043,11 @@ static int step_pipelined(fcx_engine *e, int phase, int32_t t, Plan *pl) {
     e->ev_comp.push_back(b);
     e->ev_out.push_back(c);
   }
+  // received fields: whole sources and the whole grid's gather before the first chunk
+  if (!e->received.empty()) {
+    if (int r = copy_bufs(e, received_sources(e, phase), true)) return r;
+    if (int r = run_gathers(e, phase)) return r;
+  }
   // staged (caller heap) and direct (library memory) transfers
   stage_prepare_bufs(e, pl->reads);
   stage_prepare_bufs(e, pl->writes);
@@ -3801,7 +4140,7 @@ static bool host_bound(const fcx_engine *e, const Plan *pl) {
   for (const std::vector<int> *ids : {&pl->reads, &pl->writes})
     for (int b : *ids)
       if (e->bufs[b].moves_over_link()) return true;
-  return false;
+  return false;  // (received sources alone do not make a step pipelined: they move whole)
 }
 
 extern "C" int fcx_step(fcx_engine *e, int phase, int32_t t) {
@@ -4009,6 +4348,8 @@ extern "C" int fcx_span_runs(fcx_engine *e, int phase, int32_t *h2d_copies, int3
     std::vector<int> ids;
     for (int b : k ? pl->writes : pl->reads)
       if (e->bufs[(size_t)b].span >= 0 && e->bufs[(size_t)b].n > 0) ids.push_back(b);
+    for (int b : k ? std::vector<int>() : received_sources(e, phase))
+      if (e->bufs[(size_t)b].span >= 0 && e->bufs[(size_t)b].n > 0) ids.push_back(b);
     if (int r = span_copy(e, ids, k == 0, nullptr, &n[k])) return r;
   }
   *h2d_copies = n[0];
@@ -4048,6 +4389,7 @@ extern "C" int fcx_algorithmic_bytes(fcx_engine *e, int phase, int64_t *bytes) {
     extra += e->n[0] * 8 + (e->atm_contiguous ? 0 : e->n[0] * 4) + (e->n_atmos + 1) * 4;
     extra += (int64_t)nf * (e->n[0] + e->n_atmos) * es;
   }
+  if (int r = run_gathers(e, phase, &extra)) return r;  // the gather launches of the received fields
   *bytes = b * (int64_t)e->esize + extra;
   return FCX_OK;
 }

@@ -145,6 +145,11 @@ constexpr bool skip_family(bool f32, int variant, bool ravg, bool tm1, bool merg
   if (!f32 && variant == 0 && !tm1 && !ravg && merged) return false;
   return true;
 }
+// the destination stores of the received fields' gather (fcx_kernels.hip, receive_inject_kernel):
+// 0 = plain (the flux pass reads the arrays right after), 1 = non-temporal (A/B builds)
+#ifndef FCX_RECV_NT
+#define FCX_RECV_NT 0
+#endif
 // the wave-uniform inputs in the kernels (A/B builds: 0 = every input is an array)
 #ifndef FCX_CONST_UNIFORM
 #define FCX_CONST_UNIFORM 1
@@ -444,5 +449,30 @@ int launch_regrid_csr(const int32_t *row_ptr, const int32_t *col, const double *
 // mirror of a constant field, fcx_bind_constant); f32: x is a float array and value is
 // rounded to float once
 int launch_fill(double *x, int64_t n, double value, bool f32, int64_t tpad, void *stream);
+
+// Model grid -> exchange grid gather of received fields (fcx_bind_received): the fields of one
+// (map, phase), at most kMaxReceiveFields per launch, by value.  dst[f][tiled(j, tpad)] = sum over
+// the links of exchange cell j < n, in link order from 0.0, of w * src[f][source cell]; a cell
+// without a link gets 0.0; cells past n are not written.  Injection form (idx set): idx[j] is the
+// one source cell of exchange cell j or -1, padded with -1 to a multiple of 4 entries and 16-B
+// aligned; w is one weight per exchange cell, or nullptr when every weight is 1.0.  General form
+// (idx == nullptr): CSR by exchange cell (row_ptr [n + 1], col and w per link).  Sources are
+// engine buffers in the layout tpad, or (bit f of src_plain) contiguous arrays; the engine has
+// checked every source cell against the sources' length.  f32: float fields, double arithmetic.
+constexpr int kMaxReceiveFields = 16;
+struct ReceiveArgs {
+  const int32_t *idx;
+  const double *w;
+  const int32_t *row_ptr, *col;
+  int64_t n;
+  int64_t tpad;
+  int32_t nf;
+  int32_t f32;
+  uint32_t src_plain;
+  uint32_t pad;
+  const void *src[kMaxReceiveFields];
+  void *dst[kMaxReceiveFields];
+};
+int launch_receive(const ReceiveArgs &a, void *stream);
 
 }  // namespace fcx

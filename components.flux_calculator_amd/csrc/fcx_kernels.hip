@@ -1818,6 +1818,70 @@ __global__ __launch_bounds__(256) void fill_kernel(R *x, int64_t n, R value, int
   }
 }
 
+// Model grid -> exchange grid gather of the received fields (fcx_bind_received), injection form:
+// every exchange cell has at most one link, so the map is one source cell per exchange cell
+// (idx[j], -1 = no link; the array is padded with -1 to a whole vector) and, only where some
+// weight is not 1.0, one weight per cell.  A lane owns the C consecutive cells of one 16-B
+// destination vector (C divides the layout tile, so they share one tile shift; the destinations
+// are engine buffers, 256-B aligned): its index load is one 8- or 16-B load, the index and the
+// weight are read once for all the fields of the launch, and the field loop is wave-uniform.
+// The source loads are plain cached loads -- a source value is re-read by the 4-9 cells of its
+// run -- and the destination stores are plain too: the flux pass reads the arrays right after.
+// out = 0.0 + w * x in double, no contraction (so -0.0 becomes +0.0); fp32: w * (double)x32
+// summed in double, rounded to float once.  Cells past n are not written.
+template <class R, bool W>
+__global__ __launch_bounds__(256) void receive_inject_kernel(const ReceiveArgs a) {
+  constexpr int C = 16 / sizeof(R);
+  using IV = typename std::conditional<C == 2, i2v, i4v>::type;
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; u * C < a.n; u += stride) {
+    const int64_t j0 = u * C;
+    const IV sv = *gptr(reinterpret_cast<const IV *>(a.idx + j0));  // (padded: in bounds)
+    int32_t s[C];
+    double w[C];
+#pragma unroll
+    for (int i = 0; i < C; ++i) {
+      s[i] = sv[i];
+      w[i] = 1.0;
+      if (W && j0 + i < a.n) w[i] = gptr(a.w)[j0 + i];
+    }
+    const int64_t shift = (j0 >> kLayoutShift) * a.tpad;
+    for (int f = 0; f < a.nf; ++f) {
+      const R *__restrict__ src = reinterpret_cast<const R *>(a.src[f]);
+      const int64_t stp = ((a.src_plain >> f) & 1u) ? 0 : a.tpad;
+      Vec<C, R> o;
+#pragma unroll
+      for (int i = 0; i < C; ++i) {
+        double acc = 0.0;
+        if (s[i] >= 0) {
+          const double x = (double)gptr(src)[tiled(s[i], stp)];
+          acc = acc + (W ? w[i] * x : x);
+        }
+        o.v[i] = (R)acc;
+      }
+      st<C, FCX_RECV_NT != 0, R>(reinterpret_cast<R *>(a.dst[f]) + shift, j0, a.n, o);
+    }
+  }
+}
+
+// ... general form: CSR by exchange cell in stable link order, one lane per exchange cell, the
+// row loop of atmos_kernel with a tiled destination (several links per cell: a bilinear or
+// conservative map onto an exchange grid that is not an intersection grid).
+template <class R>
+__global__ __launch_bounds__(256) void receive_csr_kernel(const ReceiveArgs a) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; d < a.n; d += stride) {
+    const int32_t k0 = gptr(a.row_ptr)[d], k1 = gptr(a.row_ptr)[d + 1];
+    for (int f = 0; f < a.nf; ++f) {
+      const R *__restrict__ src = reinterpret_cast<const R *>(a.src[f]);
+      const int64_t stp = ((a.src_plain >> f) & 1u) ? 0 : a.tpad;
+      double acc = 0.0;
+      for (int32_t k = k0; k < k1; ++k) acc = acc + gptr(a.w)[k] * (double)gptr(src)[tiled(gptr(a.col)[k], stp)];
+      gptr(reinterpret_cast<R *>(a.dst[f]))[tiled(d, a.tpad)] = (R)acc;
+    }
+  }
+}
+
 // The wide instantiations (F32Wide) are compiled in a translation unit of their own
 // (fcx_kernels_wide.hip includes this file with FCX_KERNELS_WIDE_TU set), beside this one: the
 // templates above are shared, each unit instantiates its own precisions, and these three
@@ -2280,6 +2344,34 @@ int launch_fill(double *x, int64_t n, double value, bool f32, int64_t tpad, void
                        (float)value, tpad);
   else
     hipLaunchKernelGGL(fill_kernel<double>, dim3(grid_for((n + 1) / 2)), dim3(256), 0, s, x, n, value, tpad);
+  return (int)hipGetLastError();
+}
+
+int launch_receive(const ReceiveArgs &a, void *stream) {
+  if (a.n <= 0 || a.nf <= 0) return 0;
+  if (a.nf > kMaxReceiveFields || a.tpad < 0) return (int)hipErrorInvalidValue;
+  for (int f = 0; f < a.nf; ++f)
+    if (!a.src[f] || !a.dst[f] || reinterpret_cast<uintptr_t>(a.dst[f]) % 16) return (int)hipErrorInvalidValue;
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (!a.idx) {
+    if (!a.row_ptr || !a.col || !a.w) return (int)hipErrorInvalidValue;
+    if (a.f32)
+      hipLaunchKernelGGL(receive_csr_kernel<float>, dim3(grid_for(a.n)), dim3(256), 0, s, a);
+    else
+      hipLaunchKernelGGL(receive_csr_kernel<double>, dim3(grid_for(a.n)), dim3(256), 0, s, a);
+    return (int)hipGetLastError();
+  }
+  if (reinterpret_cast<uintptr_t>(a.idx) % 16) return (int)hipErrorInvalidValue;
+  const int c = a.f32 ? 4 : 2;
+  const dim3 grid(grid_for((a.n + c - 1) / c));
+  if (a.f32 && a.w)
+    hipLaunchKernelGGL((receive_inject_kernel<float, true>), grid, dim3(256), 0, s, a);
+  else if (a.f32)
+    hipLaunchKernelGGL((receive_inject_kernel<float, false>), grid, dim3(256), 0, s, a);
+  else if (a.w)
+    hipLaunchKernelGGL((receive_inject_kernel<double, true>), grid, dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL((receive_inject_kernel<double, false>), grid, dim3(256), 0, s, a);
   return (int)hipGetLastError();
 }
 

@@ -371,6 +371,39 @@ MODULE fcx_c_api
       INTEGER(c_int32_t), INTENT(OUT) :: packed
       INTEGER(c_int) :: fcx_remap_info
     END FUNCTION
+    ! ---- receive side: a field received on the model's grid, gathered to the exchange grid on the
+    ! device (what oasis_get's remap_<grid>_<model>_to_exchangegrid.nc mapping does); 0-based links
+    FUNCTION fcx_add_receive_map(engine, grid, n_src, n_links, src_cell, dst_cell, weight, map_id) &
+        BIND(C, name='fcx_add_receive_map')
+      IMPORT :: c_int, c_int32_t, c_int64_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine, src_cell, dst_cell, weight
+      INTEGER(c_int), VALUE :: grid
+      INTEGER(c_int64_t), VALUE :: n_src, n_links
+      INTEGER(c_int32_t), INTENT(OUT) :: map_id
+      INTEGER(c_int) :: fcx_add_receive_map
+    END FUNCTION
+    FUNCTION fcx_bind_received(engine, map_id, phase, surface_type, grid, var, src, n, flags) &
+        BIND(C, name='fcx_bind_received')
+      IMPORT :: c_int, c_int32_t, c_int64_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine, src
+      INTEGER(c_int32_t), VALUE :: map_id
+      INTEGER(c_int), VALUE :: phase, surface_type, grid, var, flags
+      INTEGER(c_int64_t), VALUE :: n
+      INTEGER(c_int) :: fcx_bind_received
+    END FUNCTION
+    FUNCTION fcx_receive(engine, phase) BIND(C, name='fcx_receive')
+      IMPORT :: c_int, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int), VALUE :: phase
+      INTEGER(c_int) :: fcx_receive
+    END FUNCTION
+    FUNCTION fcx_received_info(engine, surface_type, grid, var, kind, map_id) BIND(C, name='fcx_received_info')
+      IMPORT :: c_int, c_int32_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int), VALUE :: surface_type, grid, var
+      INTEGER(c_int32_t), INTENT(OUT) :: kind, map_id
+      INTEGER(c_int) :: fcx_received_info
+    END FUNCTION
     ! ---- library-owned page-locked host memory (c_f_pointer it onto local_field arrays)
     FUNCTION fcx_host_malloc(bytes, ptr) BIND(C, name='fcx_host_malloc')
       IMPORT :: c_int, c_size_t, c_ptr

@@ -12,6 +12,8 @@
 !   fcx_register_average    for each type-0 output (optional: fused averaging)
 !   fcx_declare_constant    for each input the namelist gave a value (val_*_var_*) instead of
 !                           a sender (optional: the field is then never transferred)
+!   fcx_define_receive_map /  for each input the host receives on its model's grid (optional: the
+!   fcx_declare_received    engine expands it to the exchange grid on the device)
 !   fcx_select_outputs      once, with the host's output_field (optional: the computed fluxes no
 !                           output_field entry sends are neither downloaded nor, where nothing
 !                           else reads them, stored)
@@ -50,6 +52,7 @@ MODULE flux_calculator_calculate
     PUBLIC fcx_allocate_field, fcx_free_field
     PUBLIC fcx_declare_constant
     PUBLIC fcx_select_outputs
+    PUBLIC fcx_define_receive_map, fcx_declare_received
 
     TYPE(c_ptr), SAVE :: engine = c_null_ptr
     ! What fcx_attach bound.  The reference subroutines take the bottom model, the type count,
@@ -301,6 +304,59 @@ CONTAINS
         CALL check(fcx_bind_constant(engine, INT(surface_type, c_int), INT(which_grid, c_int), INT(my_idx, c_int), &
                                      REAL(value, c_double)), 'fcx_bind_constant')
     END SUBROUTINE fcx_declare_constant
+
+    ! A model grid -> exchange grid mapping of received fields (the links of a
+    ! mappings/remap_<grid>_<model>_to_exchangegrid.nc file, which the host reads): link k carries
+    ! weight(k) * source(src_cell(k)) to exchange cell dst_cell(k) of which_grid, both 1-based and
+    ! local to this rank, as the regridding matrices are.  n_src: cells of the model-grid arrays
+    ! on this rank.  Called between fcx_attach and fcx_commit_engine; map is what
+    ! fcx_declare_received takes.
+    SUBROUTINE fcx_define_receive_map(which_grid, n_src, src_cell, dst_cell, weight, map)
+        INTEGER,               INTENT(IN)  :: which_grid, n_src
+        INTEGER, DIMENSION(:), INTENT(IN)  :: src_cell, dst_cell
+        REAL(kind=wp), DIMENSION(:), INTENT(IN) :: weight
+        INTEGER,               INTENT(OUT) :: map
+        INTEGER(c_int32_t), ALLOCATABLE, TARGET :: s0(:), d0(:)
+        REAL(c_double),     ALLOCATABLE, TARGET :: w0(:)
+        INTEGER(c_int32_t) :: id
+        INTEGER :: n
+        IF (.NOT. c_associated(engine)) CALL contract_error('fcx_define_receive_map', 'no flux engine attached')
+        n = SIZE(src_cell)
+        IF (SIZE(dst_cell) /= n .OR. SIZE(weight) /= n) &
+            CALL contract_error('fcx_define_receive_map', 'src_cell, dst_cell and weight differ in length')
+        ALLOCATE (s0(MAX(n, 1)), d0(MAX(n, 1)), w0(MAX(n, 1)))
+        s0(1:n) = INT(src_cell - 1, c_int32_t)
+        d0(1:n) = INT(dst_cell - 1, c_int32_t)
+        w0(1:n) = REAL(weight, c_double)
+        CALL check(fcx_add_receive_map(engine, INT(which_grid, c_int), INT(n_src, c_int64_t), INT(n, c_int64_t), &
+                                       C_LOC(s0), C_LOC(d0), C_LOC(w0), id), 'fcx_add_receive_map')
+        map = INT(id)
+    END SUBROUTINE fcx_define_receive_map
+
+    ! An input field the host receives on its MODEL's grid: the host's oasis_get of the field
+    ! writes `source` (n_src cells of the map) instead of local_field's exchange-grid array, with
+    ! no OASIS remapping on the way, and the engine applies the map on the device at the start
+    ! of `phase` (FCX_PHASE_EARLY where input_field%early, else FCX_PHASE_NORMAL).  Called between
+    ! fcx_attach and fcx_commit_engine with the local_field fcx_attach bound.  From then on the
+    ! engine neither reads nor writes the exchange-grid array; aliases (distribute_input_field,
+    ! basic:334-358) follow, so an atmosphere field is declared once, for surface type 0.
+    ! `source` must stay allocated until fcx_detach (fcx_allocate_field memory, or the heap).
+    SUBROUTINE fcx_declare_received(surface_type, which_grid, my_idx, map, phase, source, local_field)
+        INTEGER,                                  INTENT(IN) :: surface_type, which_grid, my_idx, map
+        INTEGER(c_int),                           INTENT(IN) :: phase
+        REAL(kind=wp), DIMENSION(:), POINTER,     INTENT(IN) :: source
+        TYPE(local_fields_type), DIMENSION(0:,:), INTENT(IN) :: local_field
+        IF (.NOT. c_associated(engine)) CALL contract_error('fcx_declare_received', 'no flux engine attached')
+        IF (surface_type < 0 .OR. surface_type > MAX_SURFACE_TYPES .OR. which_grid < 1 .OR. which_grid > 3 .OR. &
+            my_idx < 1 .OR. my_idx > MAX_VARNAMES) CALL contract_error('fcx_declare_received', 'slot out of range')
+        IF (.NOT. ASSOCIATED(local_field(surface_type, which_grid)%var(my_idx)%field)) &
+            CALL contract_error('fcx_declare_received', 'the field is not associated')
+        IF (.NOT. ASSOCIATED(source)) CALL contract_error('fcx_declare_received', 'the source array is not associated')
+        IF (SIZE(source) < 1) CALL contract_error('fcx_declare_received', 'the source array is empty')
+        CALL check(fcx_bind_received(engine, INT(map, c_int32_t), phase, INT(surface_type, c_int), &
+                                     INT(which_grid, c_int), INT(my_idx, c_int), C_LOC(source(1)), &
+                                     INT(SIZE(source), c_int64_t), FCX_MEM_HOST), 'fcx_bind_received')
+    END SUBROUTINE fcx_declare_received
 
     ! The outputs the host never sends.  output_field holds what the send_to_* / name_send_*
     ! tables select (add_output_field, basic:170-284); every other computed flux of surface types

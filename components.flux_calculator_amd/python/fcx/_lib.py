@@ -110,6 +110,10 @@ SIGNATURES = [
     ("fcx_constant_info", _I, [_P, _I, _I, _I, _c.POINTER(_I32)]),
     ("fcx_set_output_use", _I, [_P, _I, _I, _I, _I]),
     ("fcx_output_info", _I, [_P, _I, _I, _I, _c.POINTER(_I32)]),
+    ("fcx_add_receive_map", _I, [_P, _I, _I64, _I64, _P, _P, _P, _c.POINTER(_I32)]),
+    ("fcx_bind_received", _I, [_P, _I32, _I, _I, _I, _I, _P, _I64, _I]),
+    ("fcx_receive", _I, [_P, _I]),
+    ("fcx_received_info", _I, [_P, _I, _I, _I, _c.POINTER(_I32), _c.POINTER(_I32)]),
 ]
 
 

@@ -15,7 +15,9 @@ The coupler stands in for OASIS3-MCT: `get(name, time, out)` fills the received 
 array in place (oasis_get writes through the io_field pointer), `put(name, time, array)`
 takes the sent field.  The engine's step(phase) uploads what the phase reads, runs it on
 the GPU and downloads what it writes, so the arrays the coupler sees are the host
-local_field arrays exactly as in the reference loop.
+local_field arrays exactly as in the reference loop.  A field the set-up receives on its
+model's grid (FluxCalculatorSetup.engine(receive_maps=...)) is the exception: the coupler
+fills setup.source_field[name], and the engine expands it on the device.
 """
 from .basic import PHASE_EARLY, PHASE_NORMAL
 
@@ -29,11 +31,15 @@ def _regridded(lf, f):
 def coupling_step(setup, engine, coupler, current_time):
     lf = setup.local_field
     for early, phase in ((True, PHASE_EARLY), (False, PHASE_NORMAL)):
+        sources = getattr(setup, "source_field", {})
         for f in setup.fields_in_put_order(setup.input_field, early):
-            coupler.get(f.name, current_time, lf.field[f.slot])
-        for f in setup.input_field:
-            if f.early == early and _regridded(lf, f):
-                engine.do_regridding(f.var, f.surface_type)
+            # (a field received on its model's grid: the coupler fills the source array)
+            coupler.get(f.name, current_time, sources.get(f.name, lf.field[f.slot]))
+        regridded = [f for f in setup.input_field if f.early == early and _regridded(lf, f)]
+        if any(f.name in sources for f in regridded):
+            engine.receive(phase)  # do_regridding reads the received fields as last gathered
+        for f in regridded:
+            engine.do_regridding(f.var, f.surface_type)
         engine.step(phase, current_time)
         for f in setup.fields_in_put_order(setup.output_field, early):
             coupler.put(f.name, current_time, lf.field[f.slot])

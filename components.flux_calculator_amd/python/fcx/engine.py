@@ -20,7 +20,7 @@ class Engine:
 
     def __init__(self, lf: LocalFields, num_surface_types, methods, corrections=None,
                  averages=(), regrid=None, device=0, stream=None, atmos=None, options=None, remaps=None,
-                 lib=None, commit=True, use_constants=True, output_use=None):
+                 lib=None, commit=True, use_constants=True, output_use=None, received=None):
         """atmos: exchange -> atmosphere accumulation, dict with
              local   : fcx.parallel.LocalAtmos of this rank
              fields  : [(phase, surface_type, grid, name, out_array[n_atmos])]
@@ -42,7 +42,13 @@ class Engine:
         output_use: {(surface_type, grid, name): use} declared with fcx_set_output_use after the
              arrays are bound; use is _lib.FCX_OUT_HOST / FCX_OUT_DEVICE / FCX_OUT_UNREAD or one
              of "host", "device", "unread".  The arrays of the declared slots are neither written
-             nor read by the engine from the commit on."""
+             nor read by the engine from the commit on.
+        received: model grid -> exchange grid maps of received fields, each {"grid", "n_src",
+             "src", "dst", "w" (0-based links), "fields": [(phase, surface_type, grid, name,
+             src_array[n_src])]}: the host receives the field on the model's grid into src_array
+             and the engine gathers it to the exchange grid on the device (fcx_bind_received).
+             The exchange-grid arrays of the declared slots, and of every slot aliasing them, are
+             neither read nor written by the engine from the commit on."""
         self.lib = lib if lib is not None else _lib.load()
         self.lf = lf
         self.T = int(num_surface_types)
@@ -149,6 +155,11 @@ class Engine:
                     self._keep.append(out)
                     _lib.check(self.lib.fcx_add_remap_field(h, rid.value, phase, s, g, IDX[name],
                                                             ctypes.c_void_p(data_ptr(out)), flags))
+            self.receive_maps = []  # map id of every entry of `received`
+            for rm in received or ():
+                mid = self.add_receive_map(rm["grid"], rm["n_src"], rm["src"], rm["dst"], rm["w"])
+                for phase, s, g, name, src_array in rm.get("fields", ()):
+                    self.bind_received(mid, phase, s, g, name, src_array)
             for name, value in (options or {}).items():
                 _lib.check(self.lib.fcx_set_option(h, self._option_id(name), int(value)))
             if commit:
@@ -276,6 +287,43 @@ class Engine:
         """fcx_bind_constant on an uncommitted engine (commit=False)."""
         _lib.check(self.lib.fcx_bind_constant(self.h, int(s), int(g), IDX[name], float(value)))
         self.constants[(s, g, name)] = float(value)
+
+    def add_receive_map(self, grid, n_src, src, dst, w):
+        """fcx_add_receive_map on an uncommitted engine: 0-based links model cell -> exchange cell
+        of `grid`; returns the map id."""
+        src = np.ascontiguousarray(src, dtype=np.int32)
+        dst = np.ascontiguousarray(dst, dtype=np.int32)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if not (src.shape == dst.shape == w.shape and src.ndim == 1):
+            raise ValueError("receive map: src, dst and w must be 1-D arrays of one length")
+        mid = ctypes.c_int32()
+        _lib.check(self.lib.fcx_add_receive_map(self.h, int(grid), int(n_src), src.shape[0],
+                                                ctypes.c_void_p(src.ctypes.data), ctypes.c_void_p(dst.ctypes.data),
+                                                ctypes.c_void_p(w.ctypes.data), ctypes.byref(mid)))
+        self.receive_maps.append(mid.value)
+        return mid.value
+
+    def bind_received(self, map_id, phase, s, g, name, src_array):
+        """fcx_bind_received on an uncommitted engine: slot (s, g, name) is received into
+        src_array (model grid) before `phase` and gathered through map `map_id`."""
+        if dtype_name(src_array) != self.precision:
+            raise TypeError(f"received source of {name}: {dtype_name(src_array)} array in a {self.precision} engine")
+        flags = _lib.FCX_MEM_DEVICE if is_device(src_array) else _lib.FCX_MEM_HOST
+        self._keep.append(src_array)
+        _lib.check(self.lib.fcx_bind_received(self.h, int(map_id), int(phase), int(s), int(g), IDX[name],
+                                              ctypes.c_void_p(data_ptr(src_array)), src_array.shape[0], flags))
+
+    def receive(self, phase=PHASE_ALL):
+        """fcx_receive: the phase's sources uploaded and gathered, nothing else (hosts that go on
+        with the per-call subroutines)."""
+        _lib.check(self.lib.fcx_receive(self.h, int(phase)))
+
+    def received_info(self, s, g, name):
+        """fcx_received_info: (kind, map id): kind 0 the slot is not received (map id -1), 1 it is
+        gathered into a device array of the engine's by a gather launch."""
+        k, m = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(self.lib.fcx_received_info(self.h, int(s), int(g), IDX[name], ctypes.byref(k), ctypes.byref(m)))
+        return k.value, m.value
 
     OUTPUT_USE = {"host": _lib.FCX_OUT_HOST, "device": _lib.FCX_OUT_DEVICE, "unread": _lib.FCX_OUT_UNREAD}
 

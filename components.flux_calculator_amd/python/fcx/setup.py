@@ -118,6 +118,8 @@ class FluxCalculatorSetup:
         self.local_field = LocalFields(self.grid_size, device=device, dtype=dtype)
         self.input_field = []
         self.output_field = []
+        # received name -> the model-grid array the host receives it into (engine(receive_maps=...))
+        self.source_field = {}
         self._inputs()
         for f in self.input_field:  # STEP 1.5
             self.prepare_regridding(f.var, f.surface_type)
@@ -425,12 +427,40 @@ class FluxCalculatorSetup:
         return [slot for slot in self.computed_slots()
                 if id(lf.field[slot]) not in sent and not lf.put_to.get(slot, 0)]
 
-    def engine(self, corrections=None, regrid=None, select_outputs=False, **kw):
+    def received(self, receive_maps):
+        """The `received` argument of fcx.Engine for receive_maps = {model letter: {which_grid:
+        (n_src, src, dst, w)}} (0-based links model cell -> exchange cell, what the host read from
+        mappings/remap_<grid>_<model>_to_exchangegrid.nc): every input_field of that model and
+        grid gets a model-grid source array (self.source_field[name], n_src cells) and is declared
+        with its `early` flag as the phase."""
+        out = []
+        for letter, by_grid in receive_maps.items():
+            for g, (n_src, src, dst, w) in by_grid.items():
+                fields = []
+                for f in self.input_field:
+                    if f.name[1] != letter or f.which_grid != g:
+                        continue
+                    a = self.source_field.get(f.name)
+                    if a is None:
+                        a = self.source_field[f.name] = self.local_field._new(int(n_src), 0.0)
+                    fields.append((PHASE_EARLY if f.early else PHASE_NORMAL, f.surface_type, g, f.var, a))
+                if fields:
+                    out.append({"grid": g, "n_src": int(n_src), "src": src, "dst": dst, "w": w, "fields": fields})
+        return out
+
+    def engine(self, corrections=None, regrid=None, select_outputs=False, receive_maps=None, **kw):
         """An fcx.Engine over the set-up's local_field (methods, averages, put_to).
         select_outputs: the unsent outputs are declared FCX_OUT_UNREAD (fcx_set_output_use), so
-        they are neither downloaded nor, where nothing else reads them, stored."""
+        they are neither downloaded nor, where nothing else reads them, stored.
+        receive_maps: {model letter: {which_grid: (n_src, src, dst, w)}}: the input fields of
+        those models are received on the model's grid into self.source_field[name] and gathered
+        to the exchange grid by the engine (received()); fcx.driver hands the coupler the source
+        arrays.  Without it nothing changes."""
         from . import _lib
         from .engine import Engine
+
+        if receive_maps:
+            kw["received"] = list(kw.pop("received", None) or ()) + self.received(receive_maps)
 
         if select_outputs:
             use = {slot: _lib.FCX_OUT_UNREAD for slot in self.unsent_outputs()}

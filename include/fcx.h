@@ -138,6 +138,70 @@ int fcx_bind_constant(fcx_engine *e, int surface_type, int grid, int var, double
  * constant in a device array the engine filled itself, at commit for a reader outside the flux
  * pass, later when the first launch that streams it is planned or fcx_device_ptr asks for it */
 int fcx_constant_info(const fcx_engine *e, int surface_type, int grid, int var, int32_t *kind);
+/* ---- receive side: model-grid inputs gathered to the exchange grid ----
+ * What OASIS3-MCT does inside oasis_get of a received field (remap files
+ * mappings/remap_<grid>_<model>_to_exchangegrid.nc): the host receives the field on the MODEL's
+ * grid and the engine expands it on the device, so the 4-9 copies an intersection grid holds of
+ * every atmosphere value never cross the host link.
+ *
+ * fcx_add_receive_map: a model grid -> exchange grid map: out[d] = sum over the links k with
+ * dst[k] == d, in link order from 0.0, of w[k] * src_field[src[k]]; an exchange cell without a
+ * link gets 0.0.  src: 0-based cell of the model-grid array on this rank (n_src cells), dst:
+ * 0-based exchange cell of `grid`.  Before fcx_commit only.  Checked on the host, so that no
+ * kernel ever indexes outside an array: n_src >= 1, every src in [0, n_src), every dst in
+ * [0, grid_size(grid)), every weight finite; a violation is FCX_E_ARG naming the link.  The link
+ * arrays are copied.  At fcx_commit every map in use is classified once: the injection form
+ * where no exchange cell has two links (one source index per exchange cell, a weight per cell
+ * only when some weight is not exactly 1.0), else the general form (CSR by exchange cell in
+ * stable link order).
+ *
+ * fcx_bind_received: slot (surface_type, grid, var) is received through map `map_id` into `src`
+ * before `phase` -- FCX_PHASE_EARLY or FCX_PHASE_NORMAL (FCX_PHASE_ALL is FCX_E_ARG).  Before
+ * fcx_commit only.  src holds at least n_src elements (n >= n_src; double in an fp64 engine, float
+ * in an fp32 engine); flags is FCX_MEM_HOST (heap or fcx_host_malloc memory) or FCX_MEM_DEVICE.
+ * The declaration belongs to the buffer, as a constant's does: a slot bound to an exchange-grid
+ * array turns received together with EVERY slot bound to that address (the aliases of
+ * distribute_input_field, so one declaration of an atmosphere field covers every surface type),
+ * and from then on that exchange-grid array is neither read nor written: it is not uploaded,
+ * staged, mapped or given a span.  An unbound slot becomes bound.  The exchange-grid values live
+ * in a device array of the engine's own, in the pool of arrays the whole-step launch reads (next
+ * to the filled constants, tile-blocked where the layout applies); fcx_device_ptr returns it.
+ * Cells of it past the grid size are never written.  The source array is an ordinary input
+ * mirror of n_src elements that every transport takes: the staging arena for heap arrays; direct
+ * DMA, a span or in-place use for fcx_host_malloc arrays; nothing for FCX_MEM_DEVICE; the upload
+ * thread for fcx_upload_field (of a received slot: it hands over the source).  One source array
+ * may serve several declarations of maps with the same n_src.
+ * Named FCX_E_STATE errors of fcx_plan_check / fcx_commit: the buffer is also a constant; some
+ * plan writes it (a computed flux, a 'copy' target, a regrid destination, an average's type-0
+ * output, RSDR); the map's grid differs from the declared slot's grid (an alias of the buffer on
+ * another grid must have the map's grid size: the u / v grids that ARE the t grid); two
+ * declarations of one buffer disagree (map, phase or source).
+ * When values move: fcx_upload(phase), and the upload half of fcx_step / fcx_step_async, move the
+ * phase's host sources; fcx_run(phase) begins with the phase's gather launches, before any
+ * regridding or flux pass (fcx_run_group: per member, before the merged launch; membership does
+ * not change); a host-bound step cut into pipeline chunks uploads whole sources and gathers the
+ * whole grid before its first chunk.  fcx_receive(phase) is upload plus gather alone, for hosts
+ * of the per-call face: fcx_calc_* and fcx_do_regridding read the device array as last gathered
+ * and never gather themselves.
+ * Gather launches: all received fields of one (map, phase) in one launch, at most 16 per launch.
+ * Arithmetic: fp64 engine: products and sum in double, in link order from 0.0, no contraction
+ * (a one-link cell of weight 1.0 yields 0.0 + x, so -0.0 becomes +0.0); fp32 engine:
+ * w * (double)x32 summed in double and rounded to float once, the rule of the remaps.
+ * fcx_algorithmic_bytes(phase) adds, per gather launch, the map (injection: 4 B per exchange
+ * cell, + 8 B with weights; general: 4 (grid_size + 1) + 12 n_links), n_src elements read and
+ * grid_size elements written per field, and drops nothing else; fcx_staging_bytes,
+ * fcx_zero_copy_bytes and fcx_span_runs count the sources instead of the exchange-grid arrays. */
+int fcx_add_receive_map(fcx_engine *e, int grid, int64_t n_src, int64_t n_links,
+                        const int32_t *src_cell, const int32_t *dst_cell, const double *weight,
+                        int32_t *map_id);
+int fcx_bind_received(fcx_engine *e, int32_t map_id, int phase, int surface_type, int grid,
+                      int var, double *src, int64_t n, int flags);
+int fcx_receive(fcx_engine *e, int phase);
+/* after fcx_commit: *kind = 0 the slot is not received (*map_id = -1); 1 it is gathered into a
+ * device array by a gather launch of map *map_id.  (Further kinds are reserved: a gather inside
+ * the flux pass.) */
+int fcx_received_info(const fcx_engine *e, int surface_type, int grid, int var,
+                      int32_t *kind, int32_t *map_id);
 /* What the host does with a computed output (a flux of surface types 1..T, a type-0 average, a
  * regrid destination).  The reference host sends only the fields its send_to_* / name_send_* tables
  * select (output_field, flux_calculator.F90:668-768, basic:170-284); an output it never sends
