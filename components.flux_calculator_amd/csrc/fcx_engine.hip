@@ -479,6 +479,29 @@ struct fcx_engine {
                                // declaration of the buffer that disagrees with the first
   };
   std::vector<Received> received;
+  // Field ranges and the non-finite guard (fcx_field_ranges, FCX_OPT_CHECK_FINITE).  One field
+  // of a range launch as the host keeps it: where it is read, and what it is for the report.
+  struct RangeItem {
+    const void *p;
+    int64_t n, tpad;
+    int32_t stride;
+    int kind;  // 0 an input, 1 an output, 2 an atmosphere output
+    int s, g, var;
+  };
+  int check_finite = 0;           // FCX_OPT_CHECK_FINITE: bit 0 outputs, bit 1 inputs
+  bool plan_checked = false;      // fcx_plan_check has passed (fcx_check_fields before fcx_commit)
+  DevArray<fcx_field_range> range_partial;  // [kRangePartials], one launch's per-block partials
+  DevArray<fcx_field_range> range_out;      // the finishing launches' results, a call's fields
+  fcx_field_range *range_host = nullptr;    // ... and their page-locked host image
+  size_t range_cap = 0;                     // fields both hold
+  std::vector<RangeItem> check_items;       // what the queued check launches cover, in report order
+  bool check_pending = false;               // check launches queued, verdict not read yet
+  int check_phase = 0;
+  struct CheckHit {
+    int32_t is_atmos = 0, s = 0, g = 0, var = 0;
+    int64_t cell = -1;
+    double value = 0.0;
+  } check_hit;
 
   fcx_engine() {
     for (auto &a : slot)
@@ -597,6 +620,10 @@ extern "C" int fcx_create(int device, int num_surface_types, const int32_t grid_
   // REAL(4) host opts in without a code change
   if (const char *v = std::getenv("FCX_F32_MATH"))
     if ((*v == '0' || *v == '1') && !v[1]) e->f32_math = *v == '1';
+  // FCX_CHECK_FINITE=0..3: the default of FCX_OPT_CHECK_FINITE (an explicit option still wins), so
+  // that a coupled run that went wrong is run again with the guard on without a code change
+  if (const char *v = std::getenv("FCX_CHECK_FINITE"))
+    if (*v >= '0' && *v <= '3' && !v[1]) e->check_finite = *v - '0';
   *out = e;
   return FCX_OK;
 }
@@ -620,6 +647,7 @@ extern "C" int fcx_destroy(fcx_engine *e) {
   const hipStream_t streams[] = {e->s_in, e->s_out, e->own_stream ? e->stream : nullptr};
   e->ev_stage_in = nullptr;
   stage_free(e);  // (the arena's page-locked host images)
+  if (e->range_host) (void)hipHostFree(e->range_host);
   delete e;
   for (hipEvent_t ev : events)
     if (ev) (void)hipEventDestroy(ev);
@@ -1943,7 +1971,9 @@ extern "C" int fcx_plan_check(fcx_engine *e) {
   if (int r = received_check(e)) return r;
   if (int r = settle_output_use(e)) return r;
   decide_uniform(e);
-  return plan_check_all(e);
+  if (int r = plan_check_all(e)) return r;
+  e->plan_checked = true;
+  return FCX_OK;
 }
 
 // constants_only (fcx_commit of an engine with constants): only the errors that name a constant
@@ -3830,7 +3860,304 @@ static int run_tail(fcx_engine *e, int phase) {
   return FCX_OK;
 }
 
-extern "C" int fcx_run(fcx_engine *e, int phase, int32_t t) {
+// ------------------------------------------------------------------ field ranges, non-finite guard
+
+using RangeItem = fcx_engine::RangeItem;
+
+// the first slot bound to buffer b in slot order (surface type, grid, variable: slot_name's
+// order) and the cells the engine may touch of the buffer: the largest grid it is bound on
+static bool first_slot(const fcx_engine *e, int b, int *s0, int *g0, int *v0, int64_t *n) {
+  bool found = false;
+  *n = 0;
+  for (int s = 0; s <= kMaxTypes; ++s)
+    for (int g = 1; g <= 3; ++g)
+      for (int v = 1; v <= kNumVars; ++v) {
+        if (e->slot[s][g - 1][v - 1] != b) continue;
+        if (!found) *s0 = s, *g0 = g, *v0 = v;
+        found = true;
+        *n = std::max(*n, e->n[g - 1]);
+      }
+  return found;
+}
+
+// a field buffer as a range launch reads it: where fcx_device_ptr points, in the mirrors' layout
+// when it sits in the engine's pools, contiguous otherwise (the caller's device memory, a span,
+// a host array used in place)
+static RangeItem buffer_item(const fcx_engine *e, int b, int kind) {
+  const Buffer &bf = e->bufs[(size_t)b];
+  RangeItem it{bf.dev, 0, bf.external ? 0 : e->tpad, 1, kind, 0, 0, 0};
+  first_slot(e, b, &it.s, &it.g, &it.var, &it.n);
+  return it;
+}
+
+// atmosphere output k: a plain array, its slot of the tile-blocked pool, or its column of the
+// per-cell records (atm_at), as the kernels wrote it -- no unpack launch, no download pool
+static RangeItem atmos_item(const fcx_engine *e, size_t k) {
+  const OutField &f = e->atm_fields[k];
+  return RangeItem{f.m.dev, std::max<int64_t>(e->n_atmos, 0), e->atm_records ? 0 : e->atm_out_tpad,
+                   e->atm_records ? (int32_t)e->atm_fields.size() : 1, 2, f.s, f.g, f.var};
+}
+
+// the engine's scratch for `fields` results in flight: the partials of one launch, the finishing
+// launches' results on the device and their page-locked host image (40 B per field).  Growing
+// waits for the stream and keeps what the image holds (a queued check's results).
+static int range_scratch(fcx_engine *e, size_t fields) {
+  if (!e->range_partial) HIP_TRY(e->range_partial.alloc((size_t)kRangePartials * sizeof(fcx_field_range)));
+  if (fields <= e->range_cap) return FCX_OK;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t cap = (fields + 63) / 64 * 64;
+  fcx_field_range *host = nullptr;
+  HIP_TRY(hipHostMalloc((void **)&host, cap * sizeof(fcx_field_range), kHostPinFlags));
+  if (e->range_host) {
+    std::memcpy(host, e->range_host, e->range_cap * sizeof(fcx_field_range));
+    (void)hipHostFree(e->range_host);
+  }
+  e->range_host = host;
+  e->range_cap = 0;
+  HIP_TRY(e->range_out.alloc(cap * sizeof(fcx_field_range)));
+  e->range_cap = cap;
+  return FCX_OK;
+}
+
+// the range launches of `items` on the engine stream, at most kMaxRangeFields fields each, and the
+// copy of their results into the host image from entry `at` on
+static int launch_ranges(fcx_engine *e, const std::vector<RangeItem> &items, size_t at) {
+  if (items.empty()) return FCX_OK;
+  if (int r = range_scratch(e, at + items.size())) return r;
+  for (size_t k0 = 0; k0 < items.size(); k0 += kMaxRangeFields) {
+    RangeArgs a{};
+    a.f32 = e->f32 ? 1 : 0;
+    a.partial = e->range_partial;
+    a.out = e->range_out.p + at + k0;
+    for (size_t k = k0; k < std::min(items.size(), k0 + kMaxRangeFields); ++k)
+      a.f[a.nf++] = RangeField{items[k].p, items[k].n, items[k].tpad, items[k].stride, 0};
+    const int r = launch_field_ranges(a, e->stream);
+    if (r) return fail(FCX_E_HIP, "field range launch: %s", hipGetErrorString((hipError_t)r));
+  }
+  HIP_TRY(hipMemcpyAsync(e->range_host + at, e->range_out.p + at, items.size() * sizeof(fcx_field_range), kD2H,
+                         e->stream));
+  return FCX_OK;
+}
+
+static bool slot_ok(int s, int g, int var) {
+  return s >= 0 && s <= kMaxTypes && g >= 1 && g <= 3 && var >= 1 && var <= kNumVars;
+}
+
+extern "C" int fcx_field_ranges(fcx_engine *e, int32_t n, const int32_t *slots, fcx_field_range *out) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (n < 0 || (n > 0 && (!slots || !out))) return fail(FCX_E_ARG, "fcx_field_ranges: bad arguments");
+  for (int32_t k = 0; k < n; ++k)
+    if (!slot_ok(slots[3 * k], slots[3 * k + 1], slots[3 * k + 2]))
+      return fail(FCX_E_ARG, "fcx_field_ranges: slot %d (%d,%d,%d) out of range", k, slots[3 * k], slots[3 * k + 1],
+                  slots[3 * k + 2]);
+  if (int r = check(e)) return r;
+  std::vector<RangeItem> items;
+  std::vector<int> where((size_t)n, -1);
+  for (int32_t k = 0; k < n; ++k) {
+    const int s = slots[3 * k], g = slots[3 * k + 1], v = slots[3 * k + 2];
+    const int b = e->buf(s, g, v);
+    if (b < 0)
+      return fail(FCX_E_ARG, "fcx_field_ranges: %s(%d,%s) is not bound", kVarNames[v - 1], s, grid_name(g));
+    if (int r = stale_check(e, b, "fcx_field_ranges")) return r;
+    const Buffer &bf = e->bufs[(size_t)b];
+    if (bf.constant && bf.uniform && !bf.filled) {
+      // a wave-uniform constant: answered from the value the kernels see, and it stays one
+      const double val = e->f32 ? (double)(float)bf.cval : bf.cval;
+      out[k] = fcx_field_range{val, val, 0, 0, -1};
+      if (e->n[g - 1] <= 0) out[k].min = out[k].max = std::nan("");
+      continue;
+    }
+    where[(size_t)k] = (int)items.size();
+    items.push_back(RangeItem{bf.dev, e->n[g - 1], bf.external ? 0 : e->tpad, 1, 0, s, g, v});
+  }
+  if (items.empty()) return FCX_OK;
+  const size_t at = e->check_pending ? e->check_items.size() : 0;  // (behind a queued check's results)
+  if (int r = launch_ranges(e, items, at)) return r;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (int32_t k = 0; k < n; ++k)
+    if (where[(size_t)k] >= 0) out[k] = e->range_host[at + (size_t)where[(size_t)k]];
+  return FCX_OK;
+}
+
+extern "C" int fcx_atmos_ranges(fcx_engine *e, int phase, int32_t cap, fcx_field_range *out, int32_t *n_fields) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (!n_fields || cap < 0 || (cap > 0 && !out)) return fail(FCX_E_ARG, "fcx_atmos_ranges: bad arguments");
+  if (phase < 1 || phase > 3) return fail(FCX_E_ARG, "phase %d unknown", phase);
+  if (int r = check(e)) return r;
+  std::vector<RangeItem> items;
+  for (size_t k = 0; k < e->atm_fields.size(); ++k)
+    if (e->atm_fields[k].phase & phase) items.push_back(atmos_item(e, k));
+  *n_fields = (int32_t)items.size();
+  if ((int32_t)items.size() > cap)
+    return fail(FCX_E_ARG, "fcx_atmos_ranges: phase %d has %d atmosphere outputs, cap is %d", phase, (int)items.size(), cap);
+  if (items.empty()) return FCX_OK;
+  const size_t at = e->check_pending ? e->check_items.size() : 0;
+  if (int r = launch_ranges(e, items, at)) return r;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  for (size_t k = 0; k < items.size(); ++k) out[k] = e->range_host[at + k];
+  return FCX_OK;
+}
+
+// The buffers a whole-phase run of `phase` reads (ins: every buffer a plan of the phase reads
+// without producing it, the received fields' arrays and the filled constants it streams included)
+// and stores (outs: the plans' writes -- dropped stores are not among them -- and the regrid
+// destinations), each in slot order.  Before fcx_commit the plans are built on the host only.
+static int check_lists(fcx_engine *e, int phase, std::vector<int> &ins, std::vector<int> &outs) {
+  std::set<int> r, w;
+  if (!e->committed) decide_output_keep(e);
+  auto with_plan = [&](uint32_t stages, int avg) -> int {
+    Plan dry, *pl = &dry;
+    if (e->committed) {
+      if (int rc = get_plan(e, stages, avg, &pl)) return rc;
+    } else {
+      e->plan_dry = true;
+      const int rc = build_plan(e, stages, avg, dry);
+      if (rc == FCX_OK) plan_unread_outputs(e, dry, stages, avg);
+      e->plan_dry = false;
+      if (rc) return rc;
+    }
+    r.insert(pl->reads.begin(), pl->reads.end());
+    r.insert(pl->const_reads.begin(), pl->const_reads.end());
+    w.insert(pl->writes.begin(), pl->writes.end());
+    return FCX_OK;
+  };
+  if (!e->any_regrid) {
+    if (int rc = with_plan(phase_stages(phase), phase)) return rc;
+  } else {  // the staged sequence of a regridding engine (fcx_run) and what regrid_var writes
+    static const int from_g[4] = {2, 3, 1, 1}, to_g[4] = {1, 1, 2, 3}, bit[4] = {1, 1, 2, 4};
+    std::vector<std::pair<uint32_t, int>> seq;
+    staged_sequence(phase, seq);
+    for (auto &st : seq) {
+      if (int rc = with_plan(st.first, 0)) return rc;
+      for (int s = 1; s <= kMaxTypes && st.second; ++s)
+        for (int k = 0; k < 4; ++k)
+          if ((e->put_to[s][from_g[k] - 1][var0(st.second)] & bit[k]) && e->buf(s, to_g[k], st.second) >= 0)
+            w.insert(e->buf(s, to_g[k], st.second));
+    }
+    if (int rc = with_plan(S_AVG, phase)) return rc;
+  }
+  for (int b : w) r.erase(b);
+  auto ordered = [&](const std::set<int> &ids, std::vector<int> &v) {
+    std::vector<std::pair<int, int>> keyed;
+    for (int b : ids) {
+      int s, g, var;
+      int64_t n;
+      if (first_slot(e, b, &s, &g, &var, &n)) keyed.push_back({(s * 4 + g) * 64 + var, b});
+    }
+    std::sort(keyed.begin(), keyed.end());
+    v.clear();
+    for (auto &kb : keyed) v.push_back(kb.second);
+  };
+  ordered(r, ins);
+  ordered(w, outs);
+  return FCX_OK;
+}
+
+extern "C" int fcx_check_fields(fcx_engine *e, int phase, int32_t cap, int32_t *slots, int32_t *n) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (!n || cap < 0 || (cap > 0 && !slots)) return fail(FCX_E_ARG, "fcx_check_fields: bad arguments");
+  if (phase < 1 || phase > 3) return fail(FCX_E_ARG, "phase %d unknown", phase);
+  if (!e->committed && !e->plan_checked)
+    return fail(FCX_E_STATE, "fcx_check_fields is answered after fcx_plan_check or fcx_commit");
+  std::vector<int> ins, outs, all;
+  if (e->check_finite)
+    if (int r = check_lists(e, phase, ins, outs)) return r;
+  if (e->check_finite & 2) all = ins;
+  if (e->check_finite & 1) all.insert(all.end(), outs.begin(), outs.end());
+  *n = (int32_t)all.size();
+  if ((int32_t)all.size() > cap)
+    return fail(FCX_E_ARG, "fcx_check_fields: phase %d checks %d fields, cap is %d", phase, (int)all.size(), cap);
+  for (size_t k = 0; k < all.size(); ++k) {
+    int s = 0, g = 0, var = 0;
+    int64_t cells;
+    first_slot(e, all[k], &s, &g, &var, &cells);
+    slots[3 * k] = s, slots[3 * k + 1] = g, slots[3 * k + 2] = var;
+  }
+  return FCX_OK;
+}
+
+extern "C" int fcx_check_result(const fcx_engine *e, int32_t *is_atmos, int32_t *surface_type, int32_t *grid,
+                                int32_t *var, int64_t *cell, double *value) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  const fcx_engine::CheckHit &h = e->check_hit;
+  if (is_atmos) *is_atmos = h.is_atmos;
+  if (surface_type) *surface_type = h.s;
+  if (grid) *grid = h.g;
+  if (var) *var = h.var;
+  if (cell) *cell = h.cell;
+  if (value) *value = h.value;
+  return FCX_OK;
+}
+
+// FCX_OPT_CHECK_FINITE: the range launches of a whole-phase run, queued behind everything the run
+// queued (fix-up, accumulation, boundary exchange, fcx_atmos_finish, remaps).  Inputs, outputs,
+// atmosphere outputs (when this run accumulated them): the order of the report.
+static int queue_checks(fcx_engine *e, int phase) {
+  if (!e->check_finite) return FCX_OK;
+  e->check_pending = false;
+  e->check_items.clear();
+  std::vector<int> ins, outs;
+  if (int r = check_lists(e, phase, ins, outs)) return r;
+  auto take = [&](const RangeItem &it) {
+    if (it.n > 0 && it.p) e->check_items.push_back(it);
+  };
+  if (e->check_finite & 2)
+    for (int b : ins) take(buffer_item(e, b, 0));
+  if (e->check_finite & 1) {
+    for (int b : outs) take(buffer_item(e, b, 1));
+    if (e->atm_done)
+      for (size_t k = 0; k < e->atm_fields.size(); ++k)
+        if (e->atm_fields[k].phase & phase) take(atmos_item(e, k));
+  }
+  if (int r = launch_ranges(e, e->check_items, 0)) return r;
+  e->check_phase = phase;
+  e->check_pending = !e->check_items.empty();
+  return FCX_OK;
+}
+
+// ... and their verdict, once the stream has been waited for: the first field with a NaN or an Inf
+// is FCX_E_NONFINITE; its value at first_bad is fetched now (one 8-B or 4-B copy, only on a hit)
+static int check_verdict(fcx_engine *e) {
+  if (!e->check_pending) return FCX_OK;
+  e->check_pending = false;
+  e->check_hit = fcx_engine::CheckHit{};
+  for (size_t k = 0; k < e->check_items.size(); ++k) {
+    const fcx_field_range &r = e->range_host[k];
+    if (r.n_nan + r.n_inf == 0) continue;
+    const RangeItem &it = e->check_items[k];
+    const char *src = (const char *)it.p + (size_t)(tiled(r.first_bad, it.tpad) * it.stride) * e->esize;
+    double value = 0.0;
+    if (e->f32) {
+      float v32 = 0.f;
+      HIP_TRY(hipMemcpy(&v32, src, sizeof v32, kD2H));
+      value = v32;
+    } else {
+      HIP_TRY(hipMemcpy(&value, src, sizeof value, kD2H));
+    }
+    e->check_hit.is_atmos = it.kind == 2;
+    e->check_hit.s = it.s, e->check_hit.g = it.g, e->check_hit.var = it.var;
+    e->check_hit.cell = r.first_bad;
+    e->check_hit.value = value;
+    char val[32];
+    if (std::isnan(value)) snprintf(val, sizeof val, "nan");
+    else if (std::isinf(value)) snprintf(val, sizeof val, value > 0 ? "inf" : "-inf");
+    else snprintf(val, sizeof val, "%.17g", value);
+    return fail(FCX_E_NONFINITE, "phase %d: %s%s(%d,%s) cell %lld = %s (%lld NaN, %lld Inf of %lld cells)",
+                e->check_phase, it.kind == 2 ? "atmosphere output " : "", kVarNames[it.var - 1], it.s, grid_name(it.g),
+                (long long)r.first_bad, val, (long long)r.n_nan, (long long)r.n_inf, (long long)it.n);
+  }
+  return FCX_OK;
+}
+
+// the final wait of a call that only queued (fcx_run, fcx_run_group) when a check is pending
+static int check_wait(fcx_engine *e) {
+  if (!e->check_pending) return FCX_OK;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return check_verdict(e);
+}
+
+// fcx_run without the guard's final wait: what fcx_step, fcx_step_async and fcx_run_group queue
+static int run_phase(fcx_engine *e, int phase, int32_t t) {
   if (int r = check(e)) return r;
   if (phase < 1 || phase > 3) return fail(FCX_E_ARG, "phase %d unknown", phase);
   int rc;
@@ -3863,7 +4190,13 @@ extern "C" int fcx_run(fcx_engine *e, int phase, int32_t t) {
     if (int r = get_plan(e, S_AVG, phase, &pl)) return r;
     if (int r = launch_plan(e, pl, nullptr)) return r;
   }
-  return run_tail(e, phase);
+  if (int r = run_tail(e, phase)) return r;
+  return queue_checks(e, phase);
+}
+
+extern "C" int fcx_run(fcx_engine *e, int phase, int32_t t) {
+  if (int r = run_phase(e, phase, t)) return r;
+  return check_wait(e);
 }
 
 struct GroupLaunchMember {
@@ -3939,14 +4272,24 @@ extern "C" int fcx_run_group(fcx_engine *const *es, int n, int phase, int32_t t)
   for (int i = 0; i < n; ++i) {
     fcx_engine *e = es[i];
     if (member_of[(size_t)i] < 0) {
-      if (int r = fcx_run(e, phase, t)) return r;
+      if (int r = run_phase(e, phase, t)) return r;
       continue;
     }
     e->group_members = (int)mem.size();
     e->atm_done_fused = true;
     if (int r = run_tail(e, phase)) return r;
+    if (int r = queue_checks(e, phase)) return r;
   }
-  return FCX_OK;
+  // FCX_OPT_CHECK_FINITE: every engine's work, its collectives included, is queued by now; the
+  // verdicts are read in list order and the first offender is the call's error
+  int rc = FCX_OK;
+  std::string first;
+  for (int i = 0; i < n; ++i) {
+    const int r = check_wait(es[i]);
+    if (r && !rc) rc = r, first = g_err;
+  }
+  if (rc) g_err = first;
+  return rc;
 }
 
 // the members' group arguments (af.n_tiles: each member's tile count) and their run state reset
@@ -4120,6 +4463,8 @@ static int step_pipelined(fcx_engine *e, int phase, int32_t t, Plan *pl) {
   if (int r = run_outputs(e, phase)) return r;
   HIP_TRY(hipEventRecord(e->ev_comp[K - 1], e->stream));
   HIP_TRY(hipStreamWaitEvent(e->s_out, e->ev_comp[K - 1], 0));
+  // FCX_OPT_CHECK_FINITE: once, over the whole arrays, beside the last downloads
+  if (int r = queue_checks(e, phase)) return r;
   std::vector<Xfer> xa;  // atmosphere (when this step accumulated them) and remap outputs
   if (int r = download_outputs(e, phase, e->s_out, &xa, e->atm_done)) return r;
   if (!xa.empty()) {
@@ -4133,7 +4478,7 @@ static int step_pipelined(fcx_engine *e, int phase, int32_t t, Plan *pl) {
   HIP_TRY(hipStreamSynchronize(e->s_out));
   HIP_TRY(hipStreamSynchronize(e->stream));
   if (!xa.empty()) stage_copy(e, xa, 0, -1, false);
-  return FCX_OK;
+  return check_verdict(e);
 }
 
 static bool host_bound(const fcx_engine *e, const Plan *pl) {
@@ -4154,7 +4499,7 @@ extern "C" int fcx_step(fcx_engine *e, int phase, int32_t t) {
     if (host_bound(e, pl) && pl->host.n_max >= 2 * e->min_chunk) return step_pipelined(e, phase, t, pl);
   }
   if (int r = fcx_upload(e, phase)) return r;
-  if (int r = fcx_run(e, phase, t)) return r;
+  if (int r = run_phase(e, phase, t)) return r;  // (the guard's verdict: at fcx_synchronize)
   if (int r = fcx_download(e, phase)) return r;
   return fcx_synchronize(e);
 }
@@ -4175,7 +4520,7 @@ extern "C" int fcx_step_async(fcx_engine *e, int phase, int32_t t) {
     if (host_bound(e, pl) && pl->host.n_max >= 2 * e->min_chunk) return step_pipelined(e, phase, t, pl);
   }
   if (int r = fcx_upload(e, phase)) return r;
-  if (int r = fcx_run(e, phase, t)) return r;
+  if (int r = run_phase(e, phase, t)) return r;  // (the guard's verdict: at fcx_synchronize)
   const bool keep = e->deferred_scatter;
   e->deferred_scatter = true;  // the host copies of the downloads wait for fcx_synchronize
   const int r = fcx_download(e, phase);
@@ -4188,7 +4533,8 @@ extern "C" int fcx_synchronize(fcx_engine *e) {
   if (e->committed)
     if (int r = uploader_join(e)) return r;
   HIP_TRY(hipStreamSynchronize(e->stream));
-  return stage_flush(e);
+  if (int r = stage_flush(e)) return r;
+  return check_verdict(e);  // FCX_OPT_CHECK_FINITE: the last fcx_step / fcx_step_async's
 }
 
 // one reference subroutine: upload what it reads, run, download what it writes
@@ -4513,6 +4859,11 @@ extern "C" int fcx_set_option(fcx_engine *e, int option, int64_t value) {
       if (e->committed) return fail(FCX_E_STATE, "f32_math is applied at fcx_commit");
       if (value < 0 || value > 1) return fail(FCX_E_ARG, "f32_math: 0 float arithmetic, 1 double arithmetic");
       e->f32_math = value != 0;
+      return FCX_OK;
+    case FCX_OPT_CHECK_FINITE:
+      if (e->committed) return fail(FCX_E_STATE, "check_finite is applied at fcx_commit");
+      if (value < 0 || value > 3) return fail(FCX_E_ARG, "check_finite: bit 0 the outputs, bit 1 the inputs (0..3)");
+      e->check_finite = (int)value;
       return FCX_OK;
     case FCX_OPT_TILED_LAYOUT:
       if (e->committed) return fail(FCX_E_STATE, "tiled_layout is applied at fcx_commit");

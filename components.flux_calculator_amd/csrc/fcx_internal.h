@@ -475,4 +475,31 @@ struct ReceiveArgs {
 };
 int launch_receive(const ReceiveArgs &a, void *stream);
 
+// Field ranges (fcx_field_ranges, fcx_atmos_ranges, FCX_OPT_CHECK_FINITE): min / max over the
+// cells that are not NaN, the NaN and Inf counts and the lowest cell holding either, of at most
+// kMaxRangeFields fields per launch, by value.  Cell j < n of field f is element
+// tiled(j, tpad) * stride of p: stride 1 for every field buffer (contiguous, tpad 0, or
+// tile-blocked), the record length for an atmosphere output kept as per-cell records (atm_at).
+// Cells at or past n are never read.  field_range_kernel stores one partial per (field, block)
+// into `partial` ([nf][blocks], the engine's scratch of kRangePartials entries) and
+// field_range_finish_kernel, the next launch on the stream, folds them into out[f]: no wave
+// waits for another, nothing is added to atomically, and the result does not depend on the grid.
+constexpr int kMaxRangeFields = 16;
+constexpr int kRangePartials = 2048;  // 80 KiB of scratch
+struct RangeField {
+  const void *p;
+  int64_t n;
+  int64_t tpad;
+  int32_t stride;
+  int32_t vec;  // set by launch_field_ranges: stride 1 and a 16-B aligned array, read with 16-B loads
+};
+struct RangeArgs {
+  int32_t nf;
+  int32_t f32;  // float fields (min / max widened to double, exactly)
+  RangeField f[kMaxRangeFields];
+  fcx_field_range *partial;
+  fcx_field_range *out;  // [nf], device memory
+};
+int launch_field_ranges(RangeArgs a, void *stream);
+
 }  // namespace fcx

@@ -2375,6 +2375,149 @@ int launch_receive(const ReceiveArgs &a, void *stream) {
   return (int)hipGetLastError();
 }
 
+// ---- field ranges (fcx_field_ranges, fcx_atmos_ranges, FCX_OPT_CHECK_FINITE) ----
+// One lane's running result.  min / max start at +Inf / -Inf, the identities of fmin / fmax, and
+// a NaN never enters them (fmin / fmax return the other operand: v_min / v_max in IEEE mode), so
+// "every cell was NaN" is told from the counts at the very end.  Exact and independent of order.
+template <class S>
+struct RangeAcc {
+  S mn, mx;
+  int64_t nn, ni, first;
+};
+constexpr int64_t kNoCell = INT64_MAX;
+template <class S>
+__device__ __forceinline__ void range_take(RangeAcc<S> &a, S x, int64_t j) {
+  if constexpr (sizeof(S) == 8) {
+    a.mn = __builtin_fmin(a.mn, x);
+    a.mx = __builtin_fmax(a.mx, x);
+  } else {
+    a.mn = __builtin_fminf(a.mn, x);
+    a.mx = __builtin_fmaxf(a.mx, x);
+  }
+  const bool nan = x != x;
+  const bool inf = !nan && (x == S(INFINITY) || x == -S(INFINITY));
+  a.nn += nan ? 1 : 0;
+  a.ni += inf ? 1 : 0;
+  if ((nan || inf) && j < a.first) a.first = j;
+}
+__device__ __forceinline__ void range_fold(fcx_field_range &r, const fcx_field_range &o) {
+  r.min = __builtin_fmin(r.min, o.min);
+  r.max = __builtin_fmax(r.max, o.max);
+  r.n_nan += o.n_nan;
+  r.n_inf += o.n_inf;
+  r.first_bad = o.first_bad < r.first_bad ? o.first_bad : r.first_bad;
+}
+// across the 64 lanes (every lane ends with the wave's result)
+__device__ __forceinline__ void range_wave(fcx_field_range &r) {
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) {
+    fcx_field_range o;
+    o.min = __shfl_xor(r.min, m, 64);
+    o.max = __shfl_xor(r.max, m, 64);
+    o.n_nan = __shfl_xor((long long)r.n_nan, m, 64);
+    o.n_inf = __shfl_xor((long long)r.n_inf, m, 64);
+    o.first_bad = __shfl_xor((long long)r.first_bad, m, 64);
+    range_fold(r, o);
+  }
+}
+
+// Grid (blocks, fields): block x of field y takes the 4096-cell layout tiles x, x + blocks, ...
+// of the field, so a tile's cells share one tile shift and a field's blocks are a row of the
+// grid.  A 16-B lane holds C cells; a wave instruction reads 1 KiB, a block's trip 4 KiB, and
+// the kTrips loads of a whole tile are issued before the first value is looked at.  Plain
+// loads: the arrays were just written (or are about to be read) by the flux pass.  The partial
+// last tile goes vector by vector, its partial last vector cell by cell, nothing at or past n.
+// Record fields (stride > 1) and arrays that are not 16-B aligned are read value by value:
+// correct, not fast.
+template <class S>
+__global__ __launch_bounds__(256) void field_range_kernel(const RangeArgs a) {
+  constexpr int C = 16 / sizeof(S);
+  constexpr int kTrips = (int)(kLayoutTile / (256 * C));
+  static_assert(kTrips >= 1 && kTrips * 256 * C == kLayoutTile, "a block's trips cover one layout tile");
+  using V = typename std::conditional<sizeof(S) == 8, d2, f4>::type;
+  const RangeField &fd = a.f[blockIdx.y];
+  const S *__restrict__ base = reinterpret_cast<const S *>(fd.p);
+  const int64_t n = fd.n, tiles = (n + kLayoutTile - 1) >> kLayoutShift;
+  RangeAcc<S> acc{S(INFINITY), -S(INFINITY), 0, 0, kNoCell};
+  for (int64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+    const int64_t j0 = t << kLayoutShift;
+    const S *__restrict__ tp = base + (j0 + t * fd.tpad) * fd.stride;  // tiled(j0, tpad) * stride
+    if (fd.vec && j0 + kLayoutTile <= n) {
+      V v[kTrips];
+#pragma unroll
+      for (int k = 0; k < kTrips; ++k) v[k] = gptr(reinterpret_cast<const V *>(tp))[k * 256 + threadIdx.x];
+#pragma unroll
+      for (int k = 0; k < kTrips; ++k)
+#pragma unroll
+        for (int i = 0; i < C; ++i) range_take(acc, (S)v[k][i], j0 + (int64_t)(k * 256 + threadIdx.x) * C + i);
+    } else if (fd.vec) {
+      for (int k = 0; k < kTrips; ++k) {
+        const int64_t u = (int64_t)(k * 256 + threadIdx.x) * C, j = j0 + u;
+        if (j + C <= n) {
+          const V x = *gptr(reinterpret_cast<const V *>(tp + u));
+#pragma unroll
+          for (int i = 0; i < C; ++i) range_take(acc, (S)x[i], j + i);
+        } else {
+          for (int i = 0; i < C; ++i)
+            if (j + i < n) range_take(acc, gptr(tp)[u + i], j + i);
+        }
+      }
+    } else {
+      for (int64_t u = threadIdx.x; u < kLayoutTile && j0 + u < n; u += 256)
+        range_take(acc, gptr(tp)[u * fd.stride], j0 + u);
+    }
+  }
+  fcx_field_range r{(double)acc.mn, (double)acc.mx, acc.nn, acc.ni, acc.first};
+  range_wave(r);
+  __shared__ fcx_field_range wave_part[4];
+  if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = r;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int w = 1; w < 4; ++w) range_fold(r, wave_part[w]);
+    a.partial[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = r;
+  }
+}
+
+// One wave per field folds the field's `blocks` partials and writes the result: NaN for min and
+// max when no cell was a number (every cell NaN, or n = 0), -1 for first_bad when none was bad.
+__global__ __launch_bounds__(64) void field_range_finish_kernel(const RangeArgs a, int32_t blocks) {
+  const fcx_field_range *__restrict__ p = a.partial + (int64_t)blockIdx.x * blocks;
+  fcx_field_range r{(double)INFINITY, -(double)INFINITY, 0, 0, kNoCell};
+  for (int b = threadIdx.x; b < blocks; b += 64) range_fold(r, p[b]);
+  range_wave(r);
+  if (threadIdx.x == 0) {
+    if (a.f[blockIdx.x].n - r.n_nan <= 0) r.min = r.max = (double)NAN;
+    if (r.first_bad == kNoCell) r.first_bad = -1;
+    a.out[blockIdx.x] = r;
+  }
+}
+
+// Enough blocks to fill the device (2048 of 256 threads: 8 per CU), shared by the fields of the
+// launch so that the partials stay within kRangePartials; never more than the longest field's tiles
+int launch_field_ranges(RangeArgs a, void *stream) {
+  if (a.nf <= 0) return 0;
+  if (a.nf > kMaxRangeFields || !a.partial || !a.out) return (int)hipErrorInvalidValue;
+  const size_t es = a.f32 ? 4 : 8;
+  int64_t tiles = 1;
+  for (int f = 0; f < a.nf; ++f) {
+    RangeField &fd = a.f[f];
+    if (fd.n < 0 || fd.tpad < 0 || fd.stride < 1 || (fd.n > 0 && !fd.p) || reinterpret_cast<uintptr_t>(fd.p) % es)
+      return (int)hipErrorInvalidValue;
+    fd.vec = fd.stride == 1 && reinterpret_cast<uintptr_t>(fd.p) % 16 == 0 && (fd.tpad * es) % 16 == 0;
+    tiles = std::max(tiles, (fd.n + kLayoutTile - 1) >> kLayoutShift);
+  }
+  const int blocks = (int)std::min<int64_t>(tiles, kRangePartials / a.nf);
+  hipStream_t s = reinterpret_cast<hipStream_t>(stream);
+  if (a.f32)
+    hipLaunchKernelGGL(field_range_kernel<float>, dim3(blocks, a.nf), dim3(256), 0, s, a);
+  else
+    hipLaunchKernelGGL(field_range_kernel<double>, dim3(blocks, a.nf), dim3(256), 0, s, a);
+  if (hipError_t r = hipGetLastError()) return (int)r;
+  hipLaunchKernelGGL(field_range_finish_kernel, dim3(a.nf), dim3(64), 0, s, a, (int32_t)blocks);
+  return (int)hipGetLastError();
+}
+
 #else  // FCX_KERNELS_WIDE_TU: the launchers of the F32Wide instantiations
 
 int launch_wide_fused(int variant, bool halo, bool ravg, bool nt, int blocks, hipStream_t s, const Params *dp,

@@ -27,7 +27,15 @@ MODULE fcx_c_api
                                FCX_OPT_HOST_STAGING = 15, FCX_OPT_HOST_THREADS = 16, &
                                FCX_OPT_ATMOS_HALO = 17, FCX_OPT_DEFERRED_SCATTER = 18, &
                                FCX_OPT_LIB_SPANS = 19, FCX_OPT_ATM_RECORDS = 21, &
-                               FCX_OPT_F32_MATH = 22
+                               FCX_OPT_F32_MATH = 22, FCX_OPT_CHECK_FINITE = 23
+  ! the non-finite guard (FCX_OPT_CHECK_FINITE) found a NaN or an Inf
+  INTEGER(c_int), PARAMETER :: FCX_E_NONFINITE = 7
+  ! struct fcx_field_range: min / max over the cells that are not NaN, the NaN and Inf counts, the
+  ! lowest (0-based) cell holding either, -1 when there is none
+  TYPE, BIND(C) :: fcx_field_range
+    REAL(c_double) :: vmin, vmax
+    INTEGER(c_int64_t) :: n_nan, n_inf, first_bad
+  END TYPE
   ! retired in version 3: accepted by fcx_set_option and ignored
   INTEGER(c_int), PARAMETER :: FCX_OPT_PIN_HOST = 6, FCX_OPT_CARRY_HANDOFF = 14
   ! the RCCL unique id travels between the ranks as these many bytes (MPI_Bcast)
@@ -403,6 +411,46 @@ MODULE fcx_c_api
       INTEGER(c_int), VALUE :: surface_type, grid, var
       INTEGER(c_int32_t), INTENT(OUT) :: kind, map_id
       INTEGER(c_int) :: fcx_received_info
+    END FUNCTION
+    ! ---- field ranges and the non-finite guard (the reference's DEBUG MINVAL / MAXVAL lines,
+    ! flux_calculator.F90:879-881, 921-924, 949-951, 1011-1013, on the device)
+    ! slots(3, n) = (surface_type, grid, var) per column; ranges(n) in request order
+    FUNCTION fcx_field_ranges(engine, n, slots, ranges) BIND(C, name='fcx_field_ranges')
+      IMPORT :: c_int, c_int32_t, c_ptr, fcx_field_range
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int32_t), VALUE :: n
+      INTEGER(c_int32_t), DIMENSION(*), INTENT(IN) :: slots
+      TYPE(fcx_field_range), DIMENSION(*), INTENT(OUT) :: ranges
+      INTEGER(c_int) :: fcx_field_ranges
+    END FUNCTION
+    FUNCTION fcx_atmos_ranges(engine, phase, cap, ranges, n_fields) BIND(C, name='fcx_atmos_ranges')
+      IMPORT :: c_int, c_int32_t, c_ptr, fcx_field_range
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int), VALUE :: phase
+      INTEGER(c_int32_t), VALUE :: cap
+      TYPE(fcx_field_range), DIMENSION(*), INTENT(OUT) :: ranges
+      INTEGER(c_int32_t), INTENT(OUT) :: n_fields
+      INTEGER(c_int) :: fcx_atmos_ranges
+    END FUNCTION
+    ! what FCX_OPT_CHECK_FINITE checks after a run of the phase: slots(3, n), inputs first
+    FUNCTION fcx_check_fields(engine, phase, cap, slots, n) BIND(C, name='fcx_check_fields')
+      IMPORT :: c_int, c_int32_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int), VALUE :: phase
+      INTEGER(c_int32_t), VALUE :: cap
+      INTEGER(c_int32_t), DIMENSION(*), INTENT(OUT) :: slots
+      INTEGER(c_int32_t), INTENT(OUT) :: n
+      INTEGER(c_int) :: fcx_check_fields
+    END FUNCTION
+    ! the last FCX_E_NONFINITE as numbers (cell = -1: the last checked run was clean)
+    FUNCTION fcx_check_result(engine, is_atmos, surface_type, grid, var, cell, value) &
+        BIND(C, name='fcx_check_result')
+      IMPORT :: c_int, c_int32_t, c_int64_t, c_double, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int32_t), INTENT(OUT) :: is_atmos, surface_type, grid, var
+      INTEGER(c_int64_t), INTENT(OUT) :: cell
+      REAL(c_double), INTENT(OUT) :: value
+      INTEGER(c_int) :: fcx_check_result
     END FUNCTION
     ! ---- library-owned page-locked host memory (c_f_pointer it onto local_field arrays)
     FUNCTION fcx_host_malloc(bytes, ptr) BIND(C, name='fcx_host_malloc')

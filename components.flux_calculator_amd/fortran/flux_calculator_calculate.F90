@@ -53,6 +53,7 @@ MODULE flux_calculator_calculate
     PUBLIC fcx_declare_constant
     PUBLIC fcx_select_outputs
     PUBLIC fcx_define_receive_map, fcx_declare_received
+    PUBLIC fcx_check_finite, fcx_field_range_of
 
     TYPE(c_ptr), SAVE :: engine = c_null_ptr
     ! What fcx_attach bound.  The reference subroutines take the bottom model, the type count,
@@ -411,6 +412,34 @@ CONTAINS
         CALL check(fcx_add_average(engine, phase, INT(which_grid, c_int), INT(my_idx, c_int)), &
                    'fcx_add_average')
     END SUBROUTINE fcx_register_average
+
+    ! The non-finite guard (FCX_OPT_CHECK_FINITE), before fcx_commit_engine.  what: 1 the outputs
+    ! of every phase, 3 its inputs too, 0 off.  A phase that finds a NaN or an Inf then fails
+    ! like any other engine error: fcx_run_phase / fcx_finish_phase hand the message -- phase,
+    ! field, cell, value and counts, e.g. "phase 2: TATM(1,t) cell 4097 = nan (1 NaN, 0 Inf of
+    ! 8200 cells)" -- to the registered abort routine (fcx_register_abort) before the ERROR STOP.
+    SUBROUTINE fcx_check_finite(what)
+        INTEGER, INTENT(IN) :: what
+        CALL check(fcx_set_option(engine, FCX_OPT_CHECK_FINITE, INT(what, c_int64_t)), 'fcx_check_finite')
+    END SUBROUTINE fcx_check_finite
+
+    ! MINVAL / MAXVAL of local_field(surface_type, which_grid)%var(my_idx) as the engine holds
+    ! it on the device, for a host's own DEBUG lines (flux_calculator.F90:879-881, 921-924,
+    ! 949-951, 1011-1013): the received field the calculation saw, a constant, an output that
+    ! never crosses the host link.  n_bad: cells holding a NaN or an Inf (they take no part in
+    ! vmin / vmax, which are NaN when no cell holds a number).
+    SUBROUTINE fcx_field_range_of(surface_type, which_grid, my_idx, vmin, vmax, n_bad)
+        INTEGER,  INTENT(IN)  :: surface_type, which_grid, my_idx
+        REAL(wp), INTENT(OUT) :: vmin, vmax
+        INTEGER,  INTENT(OUT) :: n_bad
+        INTEGER(c_int32_t) :: slot(3)
+        TYPE(fcx_field_range) :: r(1)
+        slot = [INT(surface_type, c_int32_t), INT(which_grid, c_int32_t), INT(my_idx, c_int32_t)]
+        CALL check(fcx_field_ranges(engine, 1_c_int32_t, slot, r), 'fcx_field_ranges')
+        vmin = REAL(r(1)%vmin, wp)
+        vmax = REAL(r(1)%vmax, wp)
+        n_bad = INT(r(1)%n_nan + r(1)%n_inf)
+    END SUBROUTINE fcx_field_range_of
 
     ! every plan the engine can launch audited on the host first (fcx_plan_check: a method
     ! that would read an input the set-up left unbound stops here with a named error, before

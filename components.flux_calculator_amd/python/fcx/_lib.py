@@ -22,6 +22,8 @@ FCX_CORR_MONTH_MAJOR = 1
 FCX_PRECISION_F64 = 0
 FCX_PRECISION_F32 = 1
 FCX_OPT_F32_MATH = 22  # an fp32 engine's fluxes computed in double (fcx_set_option)
+FCX_OPT_CHECK_FINITE = 23  # the non-finite guard: bit 0 the phase's outputs, bit 1 its inputs
+FCX_E_NONFINITE = 7
 FCX_COMM_ID_BYTES = 128
 FCX_OUT_HOST = 0
 FCX_OUT_DEVICE = 1
@@ -34,6 +36,14 @@ _I = _c.c_int
 _I32 = _c.c_int32
 _I64 = _c.c_int64
 _DP = _c.POINTER(_c.c_double)
+
+
+class FieldRangeC(_c.Structure):
+    """struct fcx_field_range"""
+    _fields_ = [("min", _c.c_double), ("max", _c.c_double), ("n_nan", _I64), ("n_inf", _I64),
+                ("first_bad", _I64)]
+
+
 SIGNATURES = [
     ("fcx_last_error", _c.c_char_p, []),
     ("fcx_version", _I, []),
@@ -114,6 +124,11 @@ SIGNATURES = [
     ("fcx_bind_received", _I, [_P, _I32, _I, _I, _I, _I, _P, _I64, _I]),
     ("fcx_receive", _I, [_P, _I]),
     ("fcx_received_info", _I, [_P, _I, _I, _I, _c.POINTER(_I32), _c.POINTER(_I32)]),
+    ("fcx_field_ranges", _I, [_P, _I32, _P, _c.POINTER(FieldRangeC)]),
+    ("fcx_atmos_ranges", _I, [_P, _I, _I32, _c.POINTER(FieldRangeC), _c.POINTER(_I32)]),
+    ("fcx_check_fields", _I, [_P, _I, _I32, _P, _c.POINTER(_I32)]),
+    ("fcx_check_result", _I, [_P, _c.POINTER(_I32), _c.POINTER(_I32), _c.POINTER(_I32), _c.POINTER(_I32),
+                              _c.POINTER(_I64), _DP]),
 ]
 
 
@@ -123,6 +138,19 @@ class FcxError(RuntimeError):
     def __init__(self, status, message):
         super().__init__(f"fcx status {status}: {message}")
         self.status = status
+
+
+class NonFiniteError(FcxError):
+    """FCX_E_NONFINITE: the non-finite guard (FCX_OPT_CHECK_FINITE) found a NaN or an Inf.  Carries
+    fcx_check_result: is_atmos, surface_type, grid, var (the id) and name, cell, value."""
+
+    def __init__(self, message, is_atmos, surface_type, grid, var, cell, value):
+        super().__init__(FCX_E_NONFINITE, message)
+        self.is_atmos = bool(is_atmos)
+        self.surface_type, self.grid, self.var = surface_type, grid, var
+        self.cell, self.value = cell, value
+        from .basic import IDX
+        self.name = next((k for k, v in IDX.items() if v == var), None)
 
 
 _lib = None
@@ -171,7 +199,17 @@ def _bind(lib, strict=True):
         fn.argtypes = args
 
 
-def check(status):
+def check(status, engine=None, lib=None):
+    """Raise FcxError for a non-zero status; with the engine handle the call ran on,
+    FCX_E_NONFINITE becomes a NonFiniteError carrying fcx_check_result."""
     if status != FCX_OK:
-        raise FcxError(status, load().fcx_last_error().decode(errors="replace"))
+        lib = lib if lib is not None else load()
+        message = lib.fcx_last_error().decode(errors="replace")
+        if status == FCX_E_NONFINITE and engine is not None:
+            a, s, g, v = _I32(), _I32(), _I32(), _I32()
+            cell, value = _I64(), _c.c_double()
+            lib.fcx_check_result(engine, _c.byref(a), _c.byref(s), _c.byref(g), _c.byref(v), _c.byref(cell),
+                                 _c.byref(value))
+            raise NonFiniteError(message, a.value, s.value, g.value, v.value, cell.value, value.value)
+        raise FcxError(status, message)
     return status

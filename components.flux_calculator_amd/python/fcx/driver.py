@@ -28,8 +28,48 @@ def _regridded(lf, f):
     return any(lf.put_to.get((s, g, f.var), 0) for s in types for g in (1, 2, 3))
 
 
-def coupling_step(setup, engine, coupler, current_time):
+VERBOSITY_LEVEL_DEBUG = 2  # flux_calculator_basic.F90:70-72
+
+
+def _log_ranges(setup, engine, early, current_time, log):
+    """The reference's DEBUG lines of a phase (flux_calculator.F90:879-881, 921-924, 949-951,
+    1011-1013): name, MINVAL, MAXVAL of every received and every sent field.  ONE fcx_field_ranges
+    call covers everything the device holds -- so a field received on its model's grid reports
+    the exchange-grid array the calculation saw, and an output kept on the device is reported at
+    all; host arrays the host filled itself are reduced where they are."""
+    import numpy as np
+
     lf = setup.local_field
+    sources = getattr(setup, "source_field", {})
+    computed = {id(lf.field[s]) for s in setup.computed_slots() if s in lf.field}
+    fields = [("received", f) for f in setup.fields_in_put_order(setup.input_field, early)]
+    fields += [("sent", f) for f in setup.fields_in_put_order(setup.output_field, early)]
+
+    def on_device(what, f):
+        # what only the device holds, or holds as the step left it: a field gathered from its
+        # model grid, a computed output, any array resident in device memory.  A host array the
+        # host itself filled (a received field, a default-valued send) is the value as it is: the
+        # engine uploads only what a calculation reads.
+        a = lf.field[f.slot]
+        return not isinstance(a, np.ndarray) or (f.name in sources if what == "received" else id(a) in computed)
+
+    asked = [f.slot for what, f in fields if on_device(what, f)]
+    ranges = iter(engine.field_ranges(asked) if asked else ())
+    for what, f in fields:
+        if on_device(what, f):
+            r = next(ranges)
+            lo, hi = r.min, r.max
+        else:
+            a = lf.field[f.slot][: lf.grid_size[f.which_grid - 1]]
+            lo, hi = (float(np.fmin.reduce(a)), float(np.fmax.reduce(a))) if a.size else (float("nan"),) * 2
+        log(f"  {what}  {f.name} at runtime={current_time} seconds: range = {lo!r} {hi!r}")
+
+
+def coupling_step(setup, engine, coupler, current_time, log=None):
+    """log: a callable taking one line; with nml["verbosity_level"] at DEBUG every phase then
+    reports the ranges of its received and sent fields (_log_ranges).  None: no range call."""
+    lf = setup.local_field
+    debug = log is not None and setup.nml.get("verbosity_level", 1) >= VERBOSITY_LEVEL_DEBUG
     for early, phase in ((True, PHASE_EARLY), (False, PHASE_NORMAL)):
         sources = getattr(setup, "source_field", {})
         for f in setup.fields_in_put_order(setup.input_field, early):
@@ -41,16 +81,19 @@ def coupling_step(setup, engine, coupler, current_time):
         for f in regridded:
             engine.do_regridding(f.var, f.surface_type)
         engine.step(phase, current_time)
+        if debug:
+            _log_ranges(setup, engine, early, current_time, log)
         for f in setup.fields_in_put_order(setup.output_field, early):
             coupler.put(f.name, current_time, lf.field[f.slot])
 
 
-def run(setup, engine, coupler, num_timesteps=None, timestep=None):
-    """DO n_timestep = 1, num_timesteps; current_time = (n_timestep - 1) * timestep."""
+def run(setup, engine, coupler, num_timesteps=None, timestep=None, log=None):
+    """DO n_timestep = 1, num_timesteps; current_time = (n_timestep - 1) * timestep.
+    log: see coupling_step."""
     n = setup.nml["num_timesteps"] if num_timesteps is None else num_timesteps
     dt = setup.nml["timestep"] if timestep is None else timestep
     for k in range(1, n + 1):
-        coupling_step(setup, engine, coupler, (k - 1) * dt)
+        coupling_step(setup, engine, coupler, (k - 1) * dt, log=log)
 
 
 __all__ = ["coupling_step", "run"]

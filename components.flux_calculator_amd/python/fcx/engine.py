@@ -1,4 +1,5 @@
 """Engine: one libfcx engine bound to a LocalFields (one rank, one GPU)."""
+import collections
 import ctypes
 import warnings
 
@@ -7,6 +8,15 @@ import numpy as np
 from . import _lib
 from .basic import FLUX_ID, IDX, METHOD_ID, PHASE_ALL, PHASE_EARLY, PHASE_NORMAL
 from .local_field import LocalFields, data_ptr, dtype_name, is_device
+
+
+FieldRange = collections.namedtuple("FieldRange", "min max n_nan n_inf first_bad")
+FieldRange.__doc__ = """struct fcx_field_range: min / max over the cells that are not NaN (both NaN when
+there is none), the NaN and Inf counts, the lowest cell holding either (-1: none)."""
+
+
+def _ranges(buf, n):
+    return [FieldRange(r.min, r.max, r.n_nan, r.n_inf, r.first_bad) for r in buf[:n]]
 
 
 class Engine:
@@ -181,17 +191,17 @@ class Engine:
         _lib.check(self.lib.fcx_upload(self.h, phase))
 
     def run(self, phase=PHASE_ALL, current_step_time=0):
-        _lib.check(self.lib.fcx_run(self.h, phase, int(current_step_time)))
+        _lib.check(self.lib.fcx_run(self.h, phase, int(current_step_time)), self.h, self.lib)
 
     def download(self, phase=PHASE_ALL):
         _lib.check(self.lib.fcx_download(self.h, phase))
 
     def step(self, phase=PHASE_ALL, current_step_time=0):
-        _lib.check(self.lib.fcx_step(self.h, phase, int(current_step_time)))
+        _lib.check(self.lib.fcx_step(self.h, phase, int(current_step_time)), self.h, self.lib)
 
     def step_async(self, phase=PHASE_ALL, current_step_time=0):
         """fcx_step_async: the step queued; the host arrays hold the outputs after synchronize()."""
-        _lib.check(self.lib.fcx_step_async(self.h, phase, int(current_step_time)))
+        _lib.check(self.lib.fcx_step_async(self.h, phase, int(current_step_time)), self.h, self.lib)
 
     def upload_field(self, surface_type, grid, name):
         """fcx_upload_field: one input field handed over (staged by the engine's upload thread)."""
@@ -207,7 +217,7 @@ class Engine:
         _lib.check(self.lib.fcx_do_regridding(self.h, IDX[name], int(surface_type)))
 
     def synchronize(self):
-        _lib.check(self.lib.fcx_synchronize(self.h))
+        _lib.check(self.lib.fcx_synchronize(self.h), self.h, self.lib)
 
     def last_kernel_ms(self):
         ms = ctypes.c_float()
@@ -245,7 +255,7 @@ class Engine:
                "atmos_in_run": 5, "pipeline_chunks": 7, "pipeline_min_chunk": 8, "zero_copy": 9,
                "timing": 10, "tiled_layout": 11, "remap_pack": 13, "host_staging": 15, "host_threads": 16,
                "atmos_halo": 17, "deferred_scatter": 18, "lib_spans": 19, "atm_records": 21,
-               "f32_math": _lib.FCX_OPT_F32_MATH}
+               "f32_math": _lib.FCX_OPT_F32_MATH, "check_finite": _lib.FCX_OPT_CHECK_FINITE}
 
     def run_atmos(self, phase=PHASE_ALL):
         _lib.check(self.lib.fcx_run_atmos(self.h, phase))
@@ -372,6 +382,54 @@ class Engine:
         _lib.check(self.lib.fcx_fused_accumulation(self.h, int(phase), ctypes.byref(on)))
         return bool(on.value)
 
+    # ---- field ranges and the non-finite guard
+    def field_ranges(self, slots):
+        """fcx_field_ranges: a FieldRange per (surface_type, grid, name) of `slots`, in request
+        order, of the device buffer behind each slot (the reference's DEBUG MINVAL / MAXVAL lines,
+        flux_calculator.F90:879-881, 949-951).  Waits for the engine's stream."""
+        slots = list(slots)
+        ids = np.array([(int(s), int(g), IDX[name] if isinstance(name, str) else int(name)) for s, g, name in slots],
+                       dtype=np.int32).reshape(-1)
+        out = (_lib.FieldRangeC * max(len(slots), 1))()
+        _lib.check(self.lib.fcx_field_ranges(self.h, len(slots), ctypes.c_void_p(ids.ctypes.data), out))
+        return _ranges(out, len(slots))
+
+    def atmos_ranges(self, phase=PHASE_ALL):
+        """fcx_atmos_ranges: a FieldRange per atmosphere output of the phase, in registration
+        order, read from the device arrays or records as they are."""
+        cap = 64
+        while True:
+            out = (_lib.FieldRangeC * cap)()
+            n = ctypes.c_int32()
+            rc = self.lib.fcx_atmos_ranges(self.h, int(phase), cap, out, ctypes.byref(n))
+            if rc == 1 and n.value > cap:
+                cap = n.value
+                continue
+            _lib.check(rc)
+            return _ranges(out, n.value)
+
+    def check_fields(self, phase=PHASE_ALL):
+        """fcx_check_fields: the (surface_type, grid, name) slots the non-finite guard checks after
+        a run of the phase, inputs first (host only; after plan_check() or commit)."""
+        cap = 3 * 11 * 35
+        ids = np.zeros(3 * cap, dtype=np.int32)
+        n = ctypes.c_int32()
+        _lib.check(self.lib.fcx_check_fields(self.h, int(phase), cap, ctypes.c_void_p(ids.ctypes.data), ctypes.byref(n)))
+        names = {v: k for k, v in IDX.items()}
+        return [(int(ids[3 * k]), int(ids[3 * k + 1]), names[int(ids[3 * k + 2])]) for k in range(n.value)]
+
+    def check_result(self):
+        """fcx_check_result of the last checked run: None when it was clean, else a dict."""
+        a, s, g, v = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        cell, value = ctypes.c_int64(), ctypes.c_double()
+        _lib.check(self.lib.fcx_check_result(self.h, ctypes.byref(a), ctypes.byref(s), ctypes.byref(g), ctypes.byref(v),
+                                             ctypes.byref(cell), ctypes.byref(value)))
+        if cell.value < 0:
+            return None
+        names = {i: k for k, i in IDX.items()}
+        return {"is_atmos": bool(a.value), "surface_type": s.value, "grid": g.value, "var": v.value,
+                "name": names.get(v.value), "cell": cell.value, "value": value.value}
+
     def close(self):
         if self.h is not None:
             self.lib.fcx_destroy(self.h)
@@ -392,7 +450,14 @@ def run_group(engines, phase=PHASE_ALL, current_step_time=0):
         return
     lib = engines[0].lib
     arr = (ctypes.c_void_p * len(engines))(*[e.h.value for e in engines])
-    _lib.check(lib.fcx_run_group(arr, len(engines), phase, int(current_step_time)))
+    rc = lib.fcx_run_group(arr, len(engines), phase, int(current_step_time))
+    if rc == _lib.FCX_E_NONFINITE:  # the first engine in list order whose check found something
+        cell = ctypes.c_int64(-1)
+        for e in engines:
+            lib.fcx_check_result(e.h, None, None, None, None, ctypes.byref(cell), None)
+            if cell.value >= 0:
+                _lib.check(rc, e.h, lib)
+    _lib.check(rc)
 
 
 def current_month(init_date, seconds):
@@ -403,4 +468,4 @@ def current_month(init_date, seconds):
     return m.value
 
 
-__all__ = ["Engine", "run_group", "current_month", "PHASE_EARLY", "PHASE_NORMAL", "PHASE_ALL"]
+__all__ = ["Engine", "FieldRange", "run_group", "current_month", "PHASE_EARLY", "PHASE_NORMAL", "PHASE_ALL"]

@@ -448,16 +448,22 @@ class FluxCalculatorSetup:
                     out.append({"grid": g, "n_src": int(n_src), "src": src, "dst": dst, "w": w, "fields": fields})
         return out
 
-    def engine(self, corrections=None, regrid=None, select_outputs=False, receive_maps=None, **kw):
+    def engine(self, corrections=None, regrid=None, select_outputs=False, receive_maps=None, check_finite=0,
+               **kw):
         """An fcx.Engine over the set-up's local_field (methods, averages, put_to).
         select_outputs: the unsent outputs are declared FCX_OUT_UNREAD (fcx_set_output_use), so
         they are neither downloaded nor, where nothing else reads them, stored.
         receive_maps: {model letter: {which_grid: (n_src, src, dst, w)}}: the input fields of
         those models are received on the model's grid into self.source_field[name] and gathered
         to the exchange grid by the engine (received()); fcx.driver hands the coupler the source
-        arrays.  Without it nothing changes."""
+        arrays.  Without it nothing changes.
+        check_finite: the non-finite guard (FCX_OPT_CHECK_FINITE): 1 every phase's outputs, 3 its
+        inputs too; a step that finds a NaN or an Inf raises fcx._lib.NonFiniteError."""
         from . import _lib
         from .engine import Engine
+
+        if check_finite:
+            kw["options"] = dict(kw.pop("options", None) or {}, check_finite=int(check_finite))
 
         if receive_maps:
             kw["received"] = list(kw.pop("received", None) or ()) + self.received(receive_maps)

@@ -62,7 +62,8 @@ enum fcx_regrid { FCX_U_TO_T = 0, FCX_V_TO_T, FCX_T_TO_U, FCX_T_TO_V };
 
 enum fcx_status {
   FCX_OK = 0, FCX_E_ARG = 1, FCX_E_STATE = 2, FCX_E_UNSUPPORTED = 3, FCX_E_HIP = 4,
-  FCX_E_MISSING = 5, FCX_E_NOMEM = 6
+  FCX_E_MISSING = 5, FCX_E_NOMEM = 6,
+  FCX_E_NONFINITE = 7 /* FCX_OPT_CHECK_FINITE found a NaN or an Inf (fcx_check_result) */
 };
 
 /* fcx_bind_field flags */
@@ -375,6 +376,53 @@ int fcx_span_runs(fcx_engine *e, int phase, int32_t *h2d_copies, int32_t *d2h_co
 /* algorithmic HBM bytes of one fcx_run(phase) (each distinct array read once, written once) */
 int fcx_algorithmic_bytes(fcx_engine *e, int phase, int64_t *bytes);
 
+/* ---- field ranges and the non-finite guard ----
+ * At verbosity_level DEBUG the reference host logs MINVAL and MAXVAL of every field it receives
+ * and sends (flux_calculator.F90:879-881, 921-924, 949-951, 1011-1013).  Here most of those fields
+ * never reach host memory (constants, outputs kept on the device, received fields, atmosphere
+ * records, device-resident hosts), so the reduction runs on the device: one streaming launch over
+ * at most 16 fields plus a one-wave-per-field finishing launch, on the engine's stream.
+ *   min, max:  over the cells that are not NaN; +-Inf takes part; both NaN when every cell is NaN
+ *              or the grid is empty.  Exact, independent of order; -0.0 and +0.0 compare equal and
+ *              either may be returned.  A float field's values are widened to double.
+ *   n_nan, n_inf: cells holding a NaN / an Inf of either sign.
+ *   first_bad: the lowest cell holding a NaN or an Inf, -1 when there is none.
+ * Cells at or past the slot's grid size never enter a result. */
+typedef struct fcx_field_range {
+  double min, max;
+  int64_t n_nan, n_inf, first_bad;
+} fcx_field_range;
+/* The ranges of n slots, slots[3 k .. 3 k + 2] = (surface_type, grid, var), into out[k], in request
+ * order (any n; launches of at most 16 fields).  After fcx_commit (FCX_E_STATE before).  It waits
+ * for the engine's stream; the results travel through a small page-locked buffer of the engine's
+ * own, 40 B per field.  A slot is read where fcx_device_ptr of it would point after a step: the
+ * engine's mirror (contiguous or tile-blocked), the caller's device array, the host array used in
+ * place under zero-copy (read through the link, as the flux kernel reads it), an engine-filled
+ * constant, a received field's exchange-grid array, an FCX_OUT_DEVICE array.  A constant no device
+ * array was filled for (fcx_constant_info 1) is answered from its value, without a launch and
+ * without filling one: min = max = the value as the kernels see it (rounded to float in an fp32
+ * engine).  A slot whose store was skipped (FCX_OUT_UNREAD, stale) is the named FCX_E_STATE error
+ * of fcx_device_ptr, before any launch; an unbound slot is FCX_E_ARG naming it. */
+int fcx_field_ranges(fcx_engine *e, int32_t n, const int32_t *slots, fcx_field_range *out);
+/* The ranges of the atmosphere outputs of `phase`, in fcx_add_atmos_field order, over the n_atmos
+ * local cells; *n_fields = their number (more than cap: FCX_E_ARG).  Read from the device arrays
+ * or per-cell records as they are: no unpack launch, no download pool.  With several ranks the
+ * values are this rank's, complete after fcx_atmos_finish (flux_calculator.F90:1011-1013). */
+int fcx_atmos_ranges(fcx_engine *e, int phase, int32_t cap, fcx_field_range *out, int32_t *n_fields);
+/* What FCX_OPT_CHECK_FINITE checks after a whole-phase run of `phase`, with the option's current
+ * value: slots[3 k .. 3 k + 2], first the inputs (bit 1), then the outputs (bit 0), each in slot
+ * order (surface type, grid, variable; a buffer under its first slot); *n = their number (more
+ * than cap: FCX_E_ARG, *n set).  The phase's atmosphere outputs are checked too and are not
+ * listed.  Host only: answered after fcx_plan_check or fcx_commit (FCX_E_STATE before either);
+ * before fcx_commit the answer is that of the plan without a fused accumulation. */
+int fcx_check_fields(fcx_engine *e, int phase, int32_t cap, int32_t *slots, int32_t *n);
+/* The last FCX_E_NONFINITE of the engine as numbers: *is_atmos 1 for an atmosphere output (then
+ * the slot is the accumulated field's), the slot, the cell (first_bad) and the value stored
+ * there.  *cell = -1 when the last checked run was clean or none has run.  NULL pointers are
+ * skipped. */
+int fcx_check_result(const fcx_engine *e, int32_t *is_atmos, int32_t *surface_type, int32_t *grid,
+                     int32_t *var, int64_t *cell, double *value);
+
 /* ---- exchange-grid -> atmosphere accumulation ----
  * What OASIS3-MCT does on oasis_put of the type-0 fields ('S A xxxx 00',
  * create_namcouple.F90:92-98): out[a] = sum_x weight[x] * field[x] over the local t-grid
@@ -574,7 +622,40 @@ enum fcx_option {
                                    fcx_commit (FCX_E_STATE afterwards); other values are
                                    FCX_E_ARG; the environment variable FCX_F32_MATH (0, 1)
                                    sets the default                                         */
-  FCX_OPT_TILED_LAYOUT = 11    /* engine-owned mirrors tile-blocked (default 1): tiles of
+  FCX_OPT_CHECK_FINITE = 23,    /* the non-finite guard (a debug mode).  0 off (default); bit 0:
+                                   the phase's outputs; bit 1: its inputs too (values 0..3).
+                                   With it on, every whole-phase run -- fcx_run, fcx_step,
+                                   fcx_step_async, fcx_run_group per member in list order, a
+                                   pipelined host step once after its last chunk, over the whole
+                                   arrays -- queues range launches (fcx_field_ranges) behind the
+                                   phase's work: fix-up, accumulation, the boundary exchange of
+                                   an attached communicator, fcx_atmos_finish, remaps.  Bit 1:
+                                   every buffer a plan of the phase reads (the received fields'
+                                   exchange-grid arrays and engine-filled constants included).
+                                   Bit 0: every buffer a plan of the phase writes and stores
+                                   (per-type fluxes, type-0 averages, regrid destinations,
+                                   RSDR) and the phase's atmosphere outputs.  Left out: outputs
+                                   whose store the plan dropped and wave-uniform constants
+                                   (nothing to read; constants are finite by fcx_bind_constant's
+                                   rule).  fcx_check_fields lists the slots.  The verdict is
+                                   read at the call's final wait: fcx_run and fcx_run_group then
+                                   end with a wait; fcx_step still downloads first, so the host
+                                   has the arrays to look at; after fcx_step_async the next
+                                   fcx_synchronize returns it.  Every collective of the call is
+                                   queued before the verdict is read, so a rank that finds a bad
+                                   value never leaves its neighbours inside the all-reduce.  A
+                                   hit returns FCX_E_NONFINITE; fcx_last_error names the first
+                                   offender -- inputs before outputs before atmosphere outputs,
+                                   then by slot -- e.g. "phase 2: TATM(1,t) cell 4097 = nan
+                                   (1 NaN, 0 Inf of 8200 cells)", and fcx_check_result gives the
+                                   same as numbers (the value: one 8-B or 4-B copy from the
+                                   device, made only on a hit).  The per-call subroutines
+                                   (fcx_calc_*, fcx_do_regridding) do not check.
+                                   fcx_algorithmic_bytes describes fcx_run's own work and does
+                                   not count the check.  Applied at fcx_commit (FCX_E_STATE
+                                   afterwards); other values are FCX_E_ARG; the environment
+                                   variable FCX_CHECK_FINITE (0..3) sets the default         */
+  FCX_OPT_TILED_LAYOUT = 11   /* engine-owned mirrors tile-blocked (default 1): tiles of
                                    4096 cells, the read-only arrays' tiles interleaved in
                                    one pool and the written arrays' in another, so a wave's
                                    accesses fall in one contiguous region (+8-10 % streaming
