@@ -332,6 +332,8 @@ struct fcx_engine {
   size_t esize = 8;       // bytes per field element
   bool f32_math = false;  // FCX_OPT_F32_MATH: an fp32 engine's fluxes computed in double
   bool wide() const { return f32 && f32_math; }  // (without effect on an fp64 engine)
+  bool cr_math = false;  // FCX_OPT_CR_MATH: an fp64 engine's exp / Exner power correctly rounded
+  bool cr() const { return !f32 && cr_math; }  // (without effect on an fp32 engine)
   // bias corrections (bias_corrections.F90)
   bool lcorr = false;
   int32_t init_date = 0;
@@ -620,6 +622,10 @@ extern "C" int fcx_create(int device, int num_surface_types, const int32_t grid_
   // REAL(4) host opts in without a code change
   if (const char *v = std::getenv("FCX_F32_MATH"))
     if ((*v == '0' || *v == '1') && !v[1]) e->f32_math = *v == '1';
+  // FCX_CR_MATH=0|1: the default of FCX_OPT_CR_MATH (an explicit option still wins), so that a
+  // coupled run or a whole test suite takes the correctly rounded functions without a code change
+  if (const char *v = std::getenv("FCX_CR_MATH"))
+    if ((*v == '0' || *v == '1') && !v[1]) e->cr_math = *v == '1';
   // FCX_CHECK_FINITE=0..3: the default of FCX_OPT_CHECK_FINITE (an explicit option still wins), so
   // that a coupled run that went wrong is run again with the guard on without a code change
   if (const char *v = std::getenv("FCX_CHECK_FINITE"))
@@ -3401,6 +3407,7 @@ static LaunchConfig plan_launch(fcx_engine *e, Plan *pl, int64_t lo, int64_t hi,
   lc.variant = (e->specialize && lc.merged) ? pl->variant : 0;
   lc.f32 = e->f32;
   lc.wide = e->wide();
+  lc.cr = e->cr();
   lc.ravg = pl->host.ravg_on != 0;
   // remap records only from the T=1 specialised fp64 kernels with two cells per lane (the
   // rule plan_fused_records applied when it built the plan)
@@ -4232,7 +4239,7 @@ static int select_group(fcx_engine *const *es, int n, int phase, int32_t t, std:
       if (ok && !mem.empty()) {
         const GroupLaunchMember &f = mem[0];
         ok = e->stream == f.e->stream && e->device == f.e->device && m.lc.f32 == f.lc.f32 &&
-             m.lc.wide == f.lc.wide &&
+             m.lc.wide == f.lc.wide && m.lc.cr == f.lc.cr &&
              m.lc.nontemporal == f.lc.nontemporal && (m.lc.halo > 0) == (f.lc.halo > 0) &&
              m.lc.ravg == f.lc.ravg && (m.pl->host.num_types == 1) == (f.pl->host.num_types == 1);
       }
@@ -4860,6 +4867,11 @@ extern "C" int fcx_set_option(fcx_engine *e, int option, int64_t value) {
       if (value < 0 || value > 1) return fail(FCX_E_ARG, "f32_math: 0 float arithmetic, 1 double arithmetic");
       e->f32_math = value != 0;
       return FCX_OK;
+    case FCX_OPT_CR_MATH:
+      if (e->committed) return fail(FCX_E_STATE, "cr_math is applied at fcx_commit");
+      if (value < 0 || value > 1) return fail(FCX_E_ARG, "cr_math: 0 the device library's exp and log, 1 correctly rounded");
+      e->cr_math = value != 0;
+      return FCX_OK;
     case FCX_OPT_CHECK_FINITE:
       if (e->committed) return fail(FCX_E_STATE, "check_finite is applied at fcx_commit");
       if (value < 0 || value > 3) return fail(FCX_E_ARG, "check_finite: bit 0 the outputs, bit 1 the inputs (0..3)");
@@ -5001,6 +5013,12 @@ extern "C" int fcx_atm_records(const fcx_engine *e, int32_t *on) {
 extern "C" int fcx_f32_math(const fcx_engine *e, int32_t *on) {
   if (!e || !on) return fail(FCX_E_ARG, "NULL argument");
   *on = e->wide() ? 1 : 0;
+  return FCX_OK;
+}
+
+extern "C" int fcx_cr_math(const fcx_engine *e, int32_t *on) {
+  if (!e || !on) return fail(FCX_E_ARG, "NULL argument");
+  *on = e->committed && e->cr() ? 1 : 0;
   return FCX_OK;
 }
 

@@ -257,6 +257,9 @@ struct LaunchConfig {
   bool f32 = false;          // fp32 fields (FCX_PRECISION_F32): 4 cells per lane
   bool wide = false;         // ... computed in double (FCX_OPT_F32_MATH; needs f32): the same
                              // launch shapes, tiles and maps, the F32Wide instantiations
+  bool cr = false;           // fp64 fields, the transcendental sites correctly rounded
+                             // (FCX_OPT_CR_MATH; never with f32): the fp64 launch shapes, the
+                             // F64Cr instantiations
   bool ravg = false;         // register averages in this plan (Params::ravg_on)
   int64_t lo = 0, hi = -1;   // cell range of this launch (lo a multiple of kChunkAlign;
                              // hi < 0: to n_max) -- the pipelined host-bound step

@@ -52,8 +52,20 @@ struct Prec<F32Wide> {
   using arith = double;
   using store = float;
 };
+// F64Cr is the fp64 engine with FCX_OPT_CR_MATH: double arrays, double arithmetic, and the three
+// transcendental sites of fcx_physics.h (the exp of QSUR and of RCO's MEVA, the Exner power)
+// correctly rounded (fcx_crmath.h).  Every other operation, layout and launch shape is the
+// fp64 engine's.
+struct F64Cr {};
+template <>
+struct Prec<F64Cr> {
+  using arith = double;
+  using store = double;
+};
 template <class PR>
 constexpr bool is_wide() { return std::is_same<PR, F32Wide>::value; }
+template <class PR>
+constexpr bool is_cr() { return std::is_same<PR, F64Cr>::value; }
 // x in the element type T (the one rounding of a wide flux on its way to memory, or the exact
 // widening of a loaded float); the same object where the types agree
 template <class T, int C>
@@ -303,7 +315,7 @@ __device__ __forceinline__ void momentum(int8_t m, bool north, const UVGridPtrs 
 // QSUR + momentum on one separate u or v grid (non-merged layout).
 // TM = 1: one wait for the grid's inputs before its first store (process, wait_inputs).
 // SKIP: QSUR of the grid may be wanted (by its momentum) though not stored (Methods::want).
-template <int C, bool NT, class R, class S, int TM, bool UNI, bool SKIP>
+template <int C, bool NT, class R, class S, int TM, bool UNI, bool SKIP, bool CR = false>
 __device__ __forceinline__ void uv_grid(const TypeParams &tp, const Methods &mt, int k, uint32_t stages, int64_t j0,
                                         int64_t n, int64_t D_) {
   const UVGridPtrs &g = tp.uv[k];
@@ -331,7 +343,7 @@ __device__ __forceinline__ void uv_grid(const TypeParams &tp, const Methods &mt,
   }
   if constexpr (TM == 1) wait_inputs();
   if (do_q) {
-    FOR_C qs.v[i] = qsur_cclm<R>(fi.v[i], ps.v[i], ts.v[i]);
+    FOR_C qs.v[i] = qsur_cclm<R, CR>(fi.v[i], ps.v[i], ts.v[i]);
     if (g.qsur) ST(g.qsur, j0, n, qs);
   }
   if (do_m) {
@@ -475,6 +487,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
                                         int64_t st_end = 0, const Early &early = Early()) {
   using R = typename Prec<PR>::arith;
   using S = typename Prec<PR>::store;
+  constexpr bool kCr = is_cr<PR>();  // the transcendental sites: correctly rounded
   static_assert(!(RAVG && TM), "register averages need more than one surface type");
   static_assert(!REC || (TM == 1 && !RAVG), "remap records: the T=1 launch");
   static_assert(!REC || std::is_same<R, S>::value, "remap records: the fp64 engine");
@@ -655,7 +668,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
           if (g.patm || cbit(cm, K_PATM)) pa_l = LDU(g.patm, cbit(cm, K_PATM), j0, nt);
           h_pa = g.patm;
           hold(K_PATM);
-          FOR_C taef.v[i] = ta_exner<R>(ta.v[i], ps.v[i], pa_l.v[i]);
+          FOR_C taef.v[i] = ta_exner<R, kCr>(ta.v[i], ps.v[i], pa_l.v[i]);
         }
         if constexpr (VAR == 1) {
           if (d_amv || d_mvp) {
@@ -727,7 +740,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       }
       // ---- calc_spec_vapor_surface(t) (calc:37-49)
       if ((stages & S_QSUR_T) && m_q == FCX_CCLM) {
-        FOR_C qs.v[i] = qsur_cclm<R>(fi.v[i], ps.v[i], ts.v[i]);
+        FOR_C qs.v[i] = qsur_cclm<R, kCr>(fi.v[i], ps.v[i], ts.v[i]);
         if (g.qsur) ST(g.qsur, j0, ns, qs);
       }
       // ---- calc_flux_mass_evap (calc:75-118), P2: TATM in the T_s slot
@@ -744,7 +757,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
             FOR_C me.v[i] = meva_cclm<R>(a.v[i], ps.v[i], qa.v[i], qs.v[i], ta.v[i], vel.v[i]);
           }
         } else if (m == FCX_RCO) {
-          FOR_C me.v[i] = meva_rco<R>(qa.v[i], ts.v[i], vel.v[i]);
+          FOR_C me.v[i] = meva_rco<R, kCr>(qa.v[i], ts.v[i], vel.v[i]);
         } else {
           have = false;  // none / copy
         }
@@ -782,7 +795,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
             FOR_C h.v[i] = hsen_cclm_num<R>(rate_num<R>(chea.v[i], vel.v[i], ps.v[i]), qa.v[i], ts.v[i], taef.v[i]);
           } else {
             const Vec<C, S> &a = (m == FCX_CCLM) ? amoi : chea;
-            FOR_C h.v[i] = hsen_cclm<R>(a.v[i], pa.v[i], ps.v[i], qa.v[i], ta.v[i], ts.v[i], vel.v[i]);
+            FOR_C h.v[i] = hsen_cclm<R, kCr>(a.v[i], pa.v[i], ps.v[i], qa.v[i], ta.v[i], ts.v[i], vel.v[i]);
           }
           if (g.hsen) ST(g.hsen, j0, ns, h);
         } else if (m == FCX_RCO) {
@@ -803,7 +816,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
           if ((stages & s_qsur) && (k == 0 ? m_qu : m_qv) == FCX_CCLM &&
               (gk.qsur || (want & (k == 0 ? W_QSUR_U : W_QSUR_V)))) {
             if (!((stages & S_QSUR_T) && m_q == FCX_CCLM)) {
-              FOR_C qs.v[i] = qsur_cclm<R>(fi.v[i], ps.v[i], ts.v[i]);
+              FOR_C qs.v[i] = qsur_cclm<R, kCr>(fi.v[i], ps.v[i], ts.v[i]);
             }
             if (gk.qsur) ST(gk.qsur, j0, ns, qs);
           }
@@ -832,8 +845,8 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       if ((stages & S_RSDR) && g.rsdr) ST(g.rsdr, j0, ns, rsdd);
     }
     if constexpr (!MERGED) {
-      if (j0 < P->n[1]) uv_grid<C, NT, R, S, TM, kUni, kSkip>(tp, mt, 0, stages, j0, P->n[1], D_);
-      if (j0 < P->n[2]) uv_grid<C, NT, R, S, TM, kUni, kSkip>(tp, mt, 1, stages, j0, P->n[2], D_);
+      if (j0 < P->n[1]) uv_grid<C, NT, R, S, TM, kUni, kSkip, kCr>(tp, mt, 0, stages, j0, P->n[1], D_);
+      if (j0 < P->n[2]) uv_grid<C, NT, R, S, TM, kUni, kSkip, kCr>(tp, mt, 1, stages, j0, P->n[2], D_);
     }
   }
 #undef HOLD
@@ -874,7 +887,8 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
 // cells [lo, hi) of the plan (lo a multiple of C), grid-stride over C-cell units
 template <int C, bool MERGED, int VAR, bool NT, class PR, int TM, bool RAVG, bool REC = false>
 // (wide register averages: 56 KiB of fp64 accumulators per block at 4 cells per lane, 2 blocks per CU)
-__global__ __launch_bounds__(256, RAVG ? (is_wide<PR>() && C == 4 ? 2 : 3) : 1) void cells_kernel(const Params *__restrict__ P,
+// (F64Cr: the double-double sites of two cells hold ~240 VGPRs; 2 = at most 256, no scratch)
+__global__ __launch_bounds__(256, RAVG ? ((is_wide<PR>() && C == 4) || (is_cr<PR>() && VAR != 3) ? 2 : 3) : 1) void cells_kernel(const Params *__restrict__ P,
                                                     const double *__restrict__ corr_m, int64_t lo,
                                                     int64_t hi) {
   const int64_t u_end = (hi + C - 1) / C;
@@ -1432,7 +1446,10 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
 #endif
 template <int C, class R, int VAR, bool NT, int TM, bool RAVG, bool REC = false, int HALO = 0>
 // (REC: the record stores took CCLM to 129 VGPRs and 3 waves per SIMD; capped at 4 blocks = 4 waves)
-__global__ __launch_bounds__(64 * atmos_waves<C>(), RAVG  ? FCX_RAVG_ATMOS_BLOCKS
+// (F64Cr, CCLM and MOM5: 2 as for the wide ones -- the correctly rounded sites of two cells
+// take 241-251 VGPRs left free, and 180-250 B of scratch under the fp64 caps of 3 and 4)
+__global__ __launch_bounds__(64 * atmos_waves<C>(), (is_cr<R>() && VAR != 3) ? FCX_WIDE_ATMOS_BLOCKS
+                                                  : RAVG  ? FCX_RAVG_ATMOS_BLOCKS
                                                   : REC ? 4
                                                   : is_wide<R>() ? FCX_WIDE_ATMOS_BLOCKS
                                                   : (C == 4 && VAR != 3) ? FCX_F32_ATMOS_BLOCKS
@@ -1497,7 +1514,8 @@ __global__ __launch_bounds__(64 * atmos_waves<C>(), RAVG  ? FCX_RAVG_ATMOS_BLOCK
 #define FCX_GROUP_BLOCKS 4
 #endif
 template <int C, class R, bool NT, int HALO, int TM = 1, bool RAVG = false>
-__global__ __launch_bounds__(64 * atmos_waves<C>(), RAVG ? FCX_RAVG_ATMOS_BLOCKS
+__global__ __launch_bounds__(64 * atmos_waves<C>(), is_cr<R>() ? FCX_WIDE_ATMOS_BLOCKS
+                                                    : RAVG ? FCX_RAVG_ATMOS_BLOCKS
                                                     : is_wide<R>() ? FCX_WIDE_ATMOS_BLOCKS
                                                     : C == 4 ? FCX_F32_ATMOS_BLOCKS : FCX_GROUP_BLOCKS) void
 cells_atmos_group_kernel(const GroupArgs g, const Params *__restrict__ P0, const Params *__restrict__ P1,
@@ -1894,6 +1912,19 @@ int launch_wide_fused(int variant, bool halo, bool ravg, bool nt, int blocks, hi
 void launch_wide_cells(int c, const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
                        const double *corr_m, int64_t lo, int64_t hi);
 void launch_wide_group(bool nt, bool halo, bool ravg, int blocks, hipStream_t s, const GroupArgs &g);
+// ... and the F64Cr instantiations (FCX_OPT_CR_MATH) in a third unit, fcx_kernels_cr.hip
+// (FCX_KERNELS_CR_TU): the sibling of every fp64 launch, behind four launchers.
+#ifndef FCX_KERNELS_CR_TU
+#define FCX_KERNELS_CR_TU 0
+#endif
+#define FCX_KERNELS_MAIN_TU (!FCX_KERNELS_WIDE_TU && !FCX_KERNELS_CR_TU)
+int launch_cr_fused(int variant, const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
+                    const double *corr_m, const AtmosFused &af, int64_t lo, int64_t hi);
+void launch_cr_cells(int c, const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
+                     const double *corr_m, int64_t lo, int64_t hi);
+void launch_cr_rec(int variant, bool nt, int blocks, hipStream_t s, const Params *dp, const double *corr_m, int64_t lo,
+                   int64_t hi);
+void launch_cr_group(bool nt, bool halo, bool ravg, int blocks, hipStream_t s, const GroupArgs &g);
 
 static int grid_for(int64_t units, int max_blocks = 256 * 8) {
   // memory-bound grid-stride: enough waves to fill 256 CUs, capped (0 = one unit per thread)
@@ -1934,19 +1965,18 @@ static void launch_c(const LaunchConfig &lc, int blocks, hipStream_t s, const Pa
   }
 }
 
-#if !FCX_KERNELS_WIDE_TU
-template <int VAR>
+// (PR: double or F64Cr)
+template <int VAR, class PR = double>
 static void launch_rec(bool nt, int blocks, hipStream_t s, const Params *dp, const double *corr_m, int64_t lo,
                        int64_t hi) {
   if (nt)
-    hipLaunchKernelGGL((cells_kernel<2, true, VAR, true, double, 1, false, true>), dim3(blocks), dim3(256), 0, s, dp,
+    hipLaunchKernelGGL((cells_kernel<2, true, VAR, true, PR, 1, false, true>), dim3(blocks), dim3(256), 0, s, dp,
                        corr_m, lo, hi);
   else
-    hipLaunchKernelGGL((cells_kernel<2, true, VAR, false, double, 1, false, true>), dim3(blocks), dim3(256), 0, s, dp,
+    hipLaunchKernelGGL((cells_kernel<2, true, VAR, false, PR, 1, false, true>), dim3(blocks), dim3(256), 0, s, dp,
                        corr_m, lo, hi);
 }
 
-#endif
 // type mode: one surface type (compile-time), several, several with register averages
 template <int C, class R>
 static void launch_r(const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
@@ -1970,7 +2000,37 @@ static void launch_atm(bool nt, int blocks, hipStream_t s, const Params *dp, con
                        dim3(64 * atmos_waves<C>()), 0, s, dp, corr_m, af, lo, hi);
 }
 
-#if !FCX_KERNELS_WIDE_TU
+// the fused launches of double fields (PR: double, or F64Cr in its own unit)
+template <int VAR, class PR>
+static int launch_atm_f64(const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
+                          const double *corr_m, const AtmosFused &af, int64_t lo, int64_t hi) {
+  const bool halo = lc.halo > 0;
+  if (hp->num_types == 1 && lc.rec) {
+    if (halo)
+      launch_atm<2, PR, VAR, 1, false, true, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+    else
+      launch_atm<2, PR, VAR, 1, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+  } else if (hp->num_types == 1) {
+    if (halo && af.rec_dense)
+      launch_atm<2, PR, VAR, 1, false, false, 2>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+    else if (halo)
+      launch_atm<2, PR, VAR, 1, false, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+    else
+      launch_atm<2, PR, VAR, 1, false>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+  } else if (lc.ravg) {
+    if constexpr (FCX_HALO_RAVG) {
+      if (halo) {
+        launch_atm<2, PR, VAR, 0, true, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+        return 0;
+      }
+    }
+    launch_atm<2, PR, VAR, 0, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+  } else
+    return (int)hipErrorInvalidValue;
+  return 0;
+}
+
+#if FCX_KERNELS_MAIN_TU
 // fused accumulation: one surface type (its fluxes), or several with the type-0 averages in
 // registers (what OASIS sends), in every precision; several types without register averages
 // are not fused
@@ -1980,6 +2040,8 @@ static int launch_atm_r(const Params *hp, const LaunchConfig &lc, int blocks, hi
   const bool halo = lc.halo > 0;
   if (halo && ((hp->num_types != 1 && !(FCX_HALO_RAVG && lc.ravg)) || lo != 0)) return (int)hipErrorInvalidValue;
   if (lc.wide && !lc.f32) return (int)hipErrorInvalidValue;
+  if (lc.cr && lc.f32) return (int)hipErrorInvalidValue;
+  if (lc.cr) return launch_cr_fused(VAR, hp, lc, blocks, s, dp, corr_m, af, lo, hi);
   if (hp->num_types == 1 && lc.wide) {  // fp32 engine computing in double: the wide kernels
     return launch_wide_fused(VAR, halo, false, lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
   } else if (hp->num_types == 1 && lc.f32) {  // fp32 engine: 4 cells per lane
@@ -1991,29 +2053,9 @@ static int launch_atm_r(const Params *hp, const LaunchConfig &lc, int blocks, hi
     if (!lc.ravg || halo) return (int)hipErrorInvalidValue;
     if (lc.wide) return launch_wide_fused(VAR, false, true, lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
     launch_atm<kF32Cpl, float, VAR, 0, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
-  } else if (hp->num_types == 1 && lc.rec) {
-    if (halo)
-      launch_atm<2, double, VAR, 1, false, true, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
-    else
-      launch_atm<2, double, VAR, 1, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
-  } else if (hp->num_types == 1) {
-    if (halo && af.rec_dense)
-      launch_atm<2, double, VAR, 1, false, false, 2>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
-    else if (halo)
-      launch_atm<2, double, VAR, 1, false, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
-    else
-      launch_atm<2, double, VAR, 1, false>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
+  } else {
+    return launch_atm_f64<VAR, double>(hp, lc, blocks, s, dp, corr_m, af, lo, hi);
   }
-  else if (lc.ravg) {
-    if constexpr (FCX_HALO_RAVG) {
-      if (halo) {
-        launch_atm<2, double, VAR, 0, true, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
-        return 0;
-      }
-    }
-    launch_atm<2, double, VAR, 0, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
-  } else
-    return (int)hipErrorInvalidValue;
   return 0;
 }
 
@@ -2083,6 +2125,10 @@ int launch_cells(const Params *hp, const Params *dp, const double *corr_m, const
   if (lc.rec) {  // remap records: the T=1 specialised fp64 kernels only (the planner's rule)
     if (lc.f32 || c != 2 || hp->num_types != 1 || !lc.merged || lc.variant < 1 || lc.variant > 3)
       return (int)hipErrorInvalidValue;
+    if (lc.cr) {
+      launch_cr_rec(lc.variant, lc.nontemporal, blocks, s, dp, corr_m, lo, hi);
+      return (int)hipGetLastError();
+    }
     switch (lc.variant) {
       case 1: launch_rec<1>(lc.nontemporal, blocks, s, dp, corr_m, lo, hi); break;
       case 2: launch_rec<2>(lc.nontemporal, blocks, s, dp, corr_m, lo, hi); break;
@@ -2090,8 +2136,10 @@ int launch_cells(const Params *hp, const Params *dp, const double *corr_m, const
     }
     return (int)hipGetLastError();
   }
-  if (lc.wide && !lc.f32) return (int)hipErrorInvalidValue;
-  if (lc.wide) {
+  if ((lc.wide && !lc.f32) || (lc.cr && lc.f32)) return (int)hipErrorInvalidValue;
+  if (lc.cr) {
+    launch_cr_cells(c, hp, lc, blocks, s, dp, corr_m, lo, hi);
+  } else if (lc.wide) {
     launch_wide_cells(c, hp, lc, blocks, s, dp, corr_m, lo, hi);
   } else if (lc.f32) {
     if (c == 4)
@@ -2116,7 +2164,7 @@ static void launch_group_h(bool halo, bool ravg, int blocks, hipStream_t s, cons
                        dim3(64 * atmos_waves<C>()), 0, s, g, p[0], p[1], p[2], p[3]);
     return;
   }
-  if constexpr (C == 2 && sizeof(R) == 8) {
+  if constexpr (C == 2 && sizeof(typename Prec<R>::store) == 8) {
     bool dense = halo;  // every member keeps per-cell records of the six fluxes
     for (int k = 0; k < g.n; ++k) dense = dense && g.m[k].af.rec_dense;
     if (dense) {
@@ -2133,7 +2181,7 @@ static void launch_group_h(bool halo, bool ravg, int blocks, hipStream_t s, cons
                        g, p[0], p[1], p[2], p[3]);
 }
 
-#if !FCX_KERNELS_WIDE_TU
+#if FCX_KERNELS_MAIN_TU
 int launch_cells_group(GroupMember *members, int n, const LaunchConfig &lc, void *stream) {
   if (n < 1 || n > kMaxGroup) return (int)hipErrorInvalidValue;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
@@ -2155,8 +2203,10 @@ int launch_cells_group(GroupMember *members, int n, const LaunchConfig &lc, void
   const int64_t kw = lc.wide ? atmos_waves<kWideCpl>() : lc.f32 ? atmos_waves<kF32Cpl>() : atmos_waves<2>();
   const int blocks = (int)std::max<int64_t>(1, (total + kw - 1) / kw);
   if (lc.ravg && lc.halo > 0) return (int)hipErrorInvalidValue;
-  if (lc.wide && !lc.f32) return (int)hipErrorInvalidValue;
-  if (lc.wide) {
+  if ((lc.wide && !lc.f32) || (lc.cr && lc.f32)) return (int)hipErrorInvalidValue;
+  if (lc.cr) {
+    launch_cr_group(lc.nontemporal, lc.halo > 0, lc.ravg, blocks, s, g);
+  } else if (lc.wide) {
     launch_wide_group(lc.nontemporal, lc.halo > 0, lc.ravg, blocks, s, g);
   } else if (lc.f32) {
     if (lc.nontemporal) launch_group_h<kF32Cpl, float, true>(lc.halo > 0, lc.ravg, blocks, s, g);
@@ -2518,7 +2568,7 @@ int launch_field_ranges(RangeArgs a, void *stream) {
   return (int)hipGetLastError();
 }
 
-#else  // FCX_KERNELS_WIDE_TU: the launchers of the F32Wide instantiations
+#elif FCX_KERNELS_WIDE_TU  // the launchers of the F32Wide instantiations
 
 int launch_wide_fused(int variant, bool halo, bool ravg, bool nt, int blocks, hipStream_t s, const Params *dp,
                       const double *corr_m, const AtmosFused &af, int64_t lo, int64_t hi) {
@@ -2553,6 +2603,42 @@ void launch_wide_group(bool nt, bool halo, bool ravg, int blocks, hipStream_t s,
     launch_group_h<kWideCpl, F32Wide, true>(halo, ravg, blocks, s, g);
   else
     launch_group_h<kWideCpl, F32Wide, false>(halo, ravg, blocks, s, g);
+}
+
+#else  // FCX_KERNELS_CR_TU: the launchers of the F64Cr instantiations
+
+int launch_cr_fused(int variant, const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
+                    const double *corr_m, const AtmosFused &af, int64_t lo, int64_t hi) {
+  switch (variant) {
+    case 1: return launch_atm_f64<1, F64Cr>(hp, lc, blocks, s, dp, corr_m, af, lo, hi);
+    case 2: return launch_atm_f64<2, F64Cr>(hp, lc, blocks, s, dp, corr_m, af, lo, hi);
+    case 3: return launch_atm_f64<3, F64Cr>(hp, lc, blocks, s, dp, corr_m, af, lo, hi);
+    default: return (int)hipErrorInvalidValue;
+  }
+}
+
+void launch_cr_cells(int c, const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
+                     const double *corr_m, int64_t lo, int64_t hi) {
+  if (c == 2)
+    launch_r<2, F64Cr>(hp, lc, blocks, s, dp, corr_m, lo, hi);
+  else
+    launch_r<1, F64Cr>(hp, lc, blocks, s, dp, corr_m, lo, hi);
+}
+
+void launch_cr_rec(int variant, bool nt, int blocks, hipStream_t s, const Params *dp, const double *corr_m, int64_t lo,
+                   int64_t hi) {
+  switch (variant) {
+    case 1: launch_rec<1, F64Cr>(nt, blocks, s, dp, corr_m, lo, hi); break;
+    case 2: launch_rec<2, F64Cr>(nt, blocks, s, dp, corr_m, lo, hi); break;
+    default: launch_rec<3, F64Cr>(nt, blocks, s, dp, corr_m, lo, hi); break;
+  }
+}
+
+void launch_cr_group(bool nt, bool halo, bool ravg, int blocks, hipStream_t s, const GroupArgs &g) {
+  if (nt)
+    launch_group_h<2, F64Cr, true>(halo, ravg, blocks, s, g);
+  else
+    launch_group_h<2, F64Cr, false>(halo, ravg, blocks, s, g);
 }
 #endif
 

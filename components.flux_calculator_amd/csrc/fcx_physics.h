@@ -12,6 +12,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
+#include "fcx_crmath.h"
 #include "fcx_internal.h"
 
 namespace fcx {
@@ -34,15 +37,29 @@ constexpr double kRv = 461.51;
 constexpr double kSigma = 5.67e-8;
 constexpr double kUmin = 0.01;
 
+// The three transcendental sites (the exp of qsur_cclm and of meva_rco, the power of pow_exner)
+// take the arithmetic policy's second half, CR: false = the device library's exp / log, as
+// every build before FCX_OPT_CR_MATH; true (fp64 only) = the correctly rounded functions of
+// fcx_crmath.h.  Nothing else in a formula depends on it.
+template <bool CR, class R>
+__device__ __forceinline__ R site_exp(R x) {
+  if constexpr (CR) {
+    static_assert(std::is_same<R, double>::value, "correctly rounded sites: the fp64 engine");
+    return cr_exp(x);
+  } else {
+    return exp(x);
+  }
+}
+
 // flux_lib/auxiliaries/flux_aux_vapor.F90:20-70 (spec_vapor_surface_cclm)
-template <class R>
+template <class R, bool CR = false>
 __device__ __forceinline__ R qsur_cclm(R fice, R ps, R ts) {
   FCX_TRIVIAL(fice + ps + ts)
   constexpr R aw = R(17.2693882), ai = R(21.8745584), t1 = R(273.16), t2w = R(35.86),
               t2i = R(7.66), p0 = R(610.78);
   const R alpha = aw + (ai - aw) * fice;
   const R t2 = t2w + (t2i - t2w) * fice;
-  const R e = p0 * exp(alpha * (ts - t1) / (ts - t2));
+  const R e = p0 * site_exp<CR>(alpha * (ts - t1) / (ts - t2));
   return R(kRd / kRv) * e / (ps - R(1.0 - kRd / kRv) * e);
 }
 
@@ -80,12 +97,12 @@ __device__ __forceinline__ R meva_cclm(R a, R ps, R qa, R qs, R ts, R vel) {
 }
 
 // flux_lib/mass/flux_mass_evap.F90:117-156 (flux_mass_evap_rco)
-template <class R>
+template <class R, bool CR = false>
 __device__ __forceinline__ R meva_rco(R qa, R ts, R vel) {
   FCX_TRIVIAL(qa + ts + vel)
   constexpr R rho_a = R(1.225), c_aw = R(1.15E-03), eps = R(0.62197), p_0 = R(1.013E+05),
               r = R(6.1078E+02), c_1 = R(17.269), c_2 = R(35.86);
-  const R e_w = r * exp(c_1 * (ts - R(273.15)) / (ts - c_2));
+  const R e_w = r * site_exp<CR>(c_1 * (ts - R(273.15)) / (ts - c_2));
   const R q_w = eps * e_w / p_0;
   return rho_a * c_aw * vel * (q_w - qa);
 }
@@ -98,8 +115,12 @@ __device__ __forceinline__ R meva_rco(R qa, R ts, R vel) {
 #ifndef FCX_POW_EXPLOG
 #define FCX_POW_EXPLOG 1
 #endif
-template <class R>
+template <class R, bool CR = false>
 __device__ __forceinline__ R pow_exner(R x, R y) {
+  if constexpr (CR) {
+    static_assert(std::is_same<R, double>::value, "correctly rounded sites: the fp64 engine");
+    return cr_pow_exner(x, y);
+  }
 #if FCX_POW_EXPLOG
   return exp(y * log(x));
 #else
@@ -110,19 +131,19 @@ __device__ __forceinline__ R pow_exner(R x, R y) {
 // flux_lib/heat/flux_heat_sensible.F90:74-94 (flux_heat_sensible_cclm; _mom5 = with CHEA).
 // T_a * EF = T_a * (p_s / p_a)**(R_d / c_p) involves atmosphere fields only: the multi-type
 // kernels form it once per cell (ta_exner) instead of one pow per surface type.
-template <class R>
+template <class R, bool CR = false>
 __device__ __forceinline__ R ta_exner(R ta, R ps, R pa) {
-  return ta * pow_exner(ps / pa, R(kRd / kCp));
+  return ta * pow_exner<R, CR>(ps / pa, R(kRd / kCp));
 }
 template <class R>
 __device__ __forceinline__ R hsen_cclm_num(R num, R qs, R ts, R taef) {
   const R fa = num / (R(kRd) * t_tilde(ts, qs));
   return fa * R(kCp) * (ts - taef);
 }
-template <class R>
+template <class R, bool CR = false>
 __device__ __forceinline__ R hsen_cclm(R a, R pa, R ps, R qs, R ta, R ts, R vel) {
   FCX_TRIVIAL(a + pa + ps + qs + ta + ts + vel)
-  return hsen_cclm_num(rate_num(a, vel, ps), qs, ts, ta_exner(ta, ps, pa));
+  return hsen_cclm_num(rate_num(a, vel, ps), qs, ts, ta_exner<R, CR>(ta, ps, pa));
 }
 
 // flux_lib/heat/flux_heat_sensible.F90:136-165 (flux_heat_sensible_rco)

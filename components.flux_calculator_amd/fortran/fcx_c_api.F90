@@ -27,7 +27,8 @@ MODULE fcx_c_api
                                FCX_OPT_HOST_STAGING = 15, FCX_OPT_HOST_THREADS = 16, &
                                FCX_OPT_ATMOS_HALO = 17, FCX_OPT_DEFERRED_SCATTER = 18, &
                                FCX_OPT_LIB_SPANS = 19, FCX_OPT_ATM_RECORDS = 21, &
-                               FCX_OPT_F32_MATH = 22, FCX_OPT_CHECK_FINITE = 23
+                               FCX_OPT_F32_MATH = 22, FCX_OPT_CHECK_FINITE = 23, &
+                               FCX_OPT_CR_MATH = 24
   ! the non-finite guard (FCX_OPT_CHECK_FINITE) found a NaN or an Inf
   INTEGER(c_int), PARAMETER :: FCX_E_NONFINITE = 7
   ! struct fcx_field_range: min / max over the cells that are not NaN, the NaN and Inf counts, the
@@ -484,6 +485,14 @@ MODULE fcx_c_api
       TYPE(c_ptr), VALUE :: engine
       INTEGER(c_int32_t), INTENT(OUT) :: on
       INTEGER(c_int) :: fcx_f32_math
+    END FUNCTION
+    ! 1 = a committed fp64 engine whose exp and Exner power are correctly rounded
+    ! (FCX_OPT_CR_MATH / FCX_CR_MATH)
+    FUNCTION fcx_cr_math(engine, on) BIND(C, name='fcx_cr_math')
+      IMPORT :: c_int, c_int32_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int32_t), INTENT(OUT) :: on
+      INTEGER(c_int) :: fcx_cr_math
     END FUNCTION
     ! after fcx_commit: 1 = the phase's exchange -> atmosphere accumulation rides in the flux launch
     FUNCTION fcx_fused_accumulation(engine, phase, on) BIND(C, name='fcx_fused_accumulation')

@@ -23,6 +23,7 @@ FCX_PRECISION_F64 = 0
 FCX_PRECISION_F32 = 1
 FCX_OPT_F32_MATH = 22  # an fp32 engine's fluxes computed in double (fcx_set_option)
 FCX_OPT_CHECK_FINITE = 23  # the non-finite guard: bit 0 the phase's outputs, bit 1 its inputs
+FCX_OPT_CR_MATH = 24  # an fp64 engine's exp and Exner power correctly rounded (fcx_set_option)
 FCX_E_NONFINITE = 7
 FCX_COMM_ID_BYTES = 128
 FCX_OUT_HOST = 0
@@ -110,6 +111,7 @@ SIGNATURES = [
     ("fcx_last_group_size", _I, [_P, _c.POINTER(_I32)]),
     ("fcx_atm_records", _I, [_P, _c.POINTER(_I32)]),
     ("fcx_f32_math", _I, [_P, _c.POINTER(_I32)]),
+    ("fcx_cr_math", _I, [_P, _c.POINTER(_I32)]),
     ("fcx_fused_accumulation", _I, [_P, _I, _c.POINTER(_I32)]),
     ("fcx_step_async", _I, [_P, _I, _I32]),
     ("fcx_upload_field", _I, [_P, _I, _I, _I]),

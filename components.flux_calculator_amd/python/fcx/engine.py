@@ -255,7 +255,8 @@ class Engine:
                "atmos_in_run": 5, "pipeline_chunks": 7, "pipeline_min_chunk": 8, "zero_copy": 9,
                "timing": 10, "tiled_layout": 11, "remap_pack": 13, "host_staging": 15, "host_threads": 16,
                "atmos_halo": 17, "deferred_scatter": 18, "lib_spans": 19, "atm_records": 21,
-               "f32_math": _lib.FCX_OPT_F32_MATH, "check_finite": _lib.FCX_OPT_CHECK_FINITE}
+               "f32_math": _lib.FCX_OPT_F32_MATH, "check_finite": _lib.FCX_OPT_CHECK_FINITE,
+               "cr_math": _lib.FCX_OPT_CR_MATH}
 
     def run_atmos(self, phase=PHASE_ALL):
         _lib.check(self.lib.fcx_run_atmos(self.h, phase))
@@ -373,6 +374,13 @@ class Engine:
         """True when this is an fp32 engine computing its fluxes in double (fcx_f32_math)."""
         on = ctypes.c_int32()
         _lib.check(self.lib.fcx_f32_math(self.h, ctypes.byref(on)))
+        return bool(on.value)
+
+    def cr_math(self):
+        """True when this is a committed fp64 engine whose exp and Exner power are correctly
+        rounded (fcx_cr_math)."""
+        on = ctypes.c_int32()
+        _lib.check(self.lib.fcx_cr_math(self.h, ctypes.byref(on)))
         return bool(on.value)
 
     def fused_accumulation(self, phase=PHASE_ALL):

@@ -6,10 +6,16 @@ HERE="$(cd "$(dirname "$0")/.." && pwd)"
 OUT="$1"; shift
 mkdir -p "$OUT/obj"
 FLAGS="-DFCX_AB_BUILD --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -I$HERE/csrc -I$HERE/../include"
-/opt/rocm/bin/hipcc $FLAGS "$@" -c "$HERE/csrc/fcx_kernels.hip" -o "$OUT/obj/fcx_kernels.o" &
-/opt/rocm/bin/hipcc $FLAGS "$@" -c "$HERE/csrc/fcx_kernels_wide.hip" -o "$OUT/obj/fcx_kernels_wide.o" &
-/opt/rocm/bin/hipcc $FLAGS "$@" -c "$HERE/csrc/fcx_engine.hip" -o "$OUT/obj/fcx_engine.o" &
-wait
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libfcx.so" "$OUT/obj/fcx_kernels.o" "$OUT/obj/fcx_kernels_wide.o" \
-  "$OUT/obj/fcx_engine.o"
+# the Makefile's translation units, side by side; each job is waited for by its pid, so a
+# failed compile fails the script
+UNITS="fcx_kernels fcx_kernels_wide fcx_kernels_cr fcx_engine"
+OBJS=""
+PIDS=""
+for u in $UNITS; do
+  /opt/rocm/bin/hipcc $FLAGS "$@" -c "$HERE/csrc/$u.hip" -o "$OUT/obj/$u.o" &
+  PIDS="$PIDS $!"
+  OBJS="$OBJS $OUT/obj/$u.o"
+done
+for p in $PIDS; do wait "$p"; done
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libfcx.so" $OBJS
 python3 "$HERE/tools/unversion_needed.py" "$OUT/libfcx.so"

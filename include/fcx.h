@@ -302,6 +302,10 @@ int fcx_atm_records(const fcx_engine *e, int32_t *on);
 /* 1 when the engine is an fp32 engine whose fluxes are computed in double (FCX_OPT_F32_MATH, by
  * the option or the environment's default), 0 otherwise; before fcx_commit: what it would apply */
 int fcx_f32_math(const fcx_engine *e, int32_t *on);
+/* 1 when the engine is a committed fp64 engine that runs the correctly rounded kernels
+ * (FCX_OPT_CR_MATH, by the option or the environment's default); 0 before fcx_commit, on an
+ * fp32 engine and with the option off */
+int fcx_cr_math(const fcx_engine *e, int32_t *on);
 /* after fcx_commit: 1 when the phase's exchange -> atmosphere accumulation rides inside the flux
  * launch (no second pass over the fields), 0 when atmos_kernel runs it; FCX_E_STATE before commit,
  * FCX_E_ARG for a phase outside 1..3 or a NULL pointer.  It may build the phase's plan (as the
@@ -655,6 +659,37 @@ enum fcx_option {
                                    not count the check.  Applied at fcx_commit (FCX_E_STATE
                                    afterwards); other values are FCX_E_ARG; the environment
                                    variable FCX_CHECK_FINITE (0..3) sets the default         */
+  FCX_OPT_CR_MATH = 24,         /* the transcendental functions of an fp64 engine.  0 (default):
+                                   the device library's exp and log, as ever.  1: the three
+                                   places where a flux formula leaves IEEE arithmetic -- the
+                                   exp of QSUR (CCLM), the exp of RCO's MEVA and the Exner
+                                   power (p_s / p_a)**(R_d / c_p) of the CCLM / MOM5 HSEN --
+                                   return the CORRECTLY ROUNDED value: the double nearest the
+                                   exact exp(a) or x**y, ties to even, for the argument the
+                                   formula forms in double.  Every other operation already is
+                                   one IEEE operation in the reference's order, so with the
+                                   option on every flux is a function of the input bits alone:
+                                   it does not move with the ROCm release, and it differs from
+                                   a host's result only where that host's libm misrounds.
+                                   Domain: exp for 2^-30 <= |a| <= 690; the power for 0.5 <=
+                                   x <= 2, x != 1 and 1/16 <= y <= 1.  Outside it (NaN, Inf,
+                                   zero or negative pressure ratios, overflow, TSUR within
+                                   1e-8 K of the formula's reference temperature) the site
+                                   returns what the default build returns.  The evaluation's
+                                   error bound is 2^-100 relative (csrc/fcx_crmath.h): an
+                                   expected 4e-5 misrounded values in 2.5e9.  Every fp64 launch
+                                   has its sibling (T = 1 specialised and generic, several
+                                   types, register averages, fused accumulation with records or
+                                   halo tiles, remap records, the group launch, the per-call
+                                   subroutines); no plan falls back and none is refused.
+                                   fcx_run_group merges engines that agree on the option.
+                                   Unchanged: arrays, layout, transports, constants, output-use
+                                   rules, received fields, the non-finite guard,
+                                   fcx_algorithmic_bytes.  A visibly slower step.
+                                   Accepted and without effect on an fp32 engine, with or
+                                   without FCX_OPT_F32_MATH.  Applied at fcx_commit
+                                   (FCX_E_STATE afterwards); other values are FCX_E_ARG; the
+                                   environment variable FCX_CR_MATH (0, 1) sets the default  */
   FCX_OPT_TILED_LAYOUT = 11   /* engine-owned mirrors tile-blocked (default 1): tiles of
                                    4096 cells, the read-only arrays' tiles interleaved in
                                    one pool and the written arrays' in another, so a wave's
