@@ -32,6 +32,7 @@
 
 #include "fcx_copy_pool.h"
 #include "fcx_internal.h"
+#include "fcx_exactsum.h"
 
 using namespace fcx;
 
@@ -504,6 +505,20 @@ struct fcx_engine {
     int64_t cell = -1;
     double value = 0.0;
   } check_hit;
+  // Exact integrals (fcx_field_integrals, fcx_atmos_integrals).  Areas of the exchange grids
+  // (0..2) and of the atmosphere cells (3): the caller's values wait on the host until the first
+  // integral call after fcx_commit uploads them, once, into a contiguous array of their own --
+  // no pool, no transport, no plan knows them.
+  struct Areas {
+    std::vector<double> host;  // set and not uploaded yet
+    DevArray<double> dev;
+    bool set = false;
+  } areas[4];
+  DevArray<int64_t> sum_partial;        // [kRangePartials][kSumWords], one launch's per-block partials
+  DevArray<fcx_exact_sum> sum_out;      // the finishing launches' results, a call's fields
+  fcx_exact_sum *sum_host = nullptr;    // ... and their page-locked host image
+  size_t sum_cap = 0;                   // fields both hold
+  bool sum_baseline = false;            // FCX_OPT_SUM_BASELINE
 
   fcx_engine() {
     for (auto &a : slot)
@@ -654,6 +669,7 @@ extern "C" int fcx_destroy(fcx_engine *e) {
   e->ev_stage_in = nullptr;
   stage_free(e);  // (the arena's page-locked host images)
   if (e->range_host) (void)hipHostFree(e->range_host);
+  if (e->sum_host) (void)hipHostFree(e->sum_host);
   delete e;
   for (hipEvent_t ev : events)
     if (ev) (void)hipEventDestroy(ev);
@@ -4005,6 +4021,217 @@ extern "C" int fcx_atmos_ranges(fcx_engine *e, int phase, int32_t cap, fcx_field
   return FCX_OK;
 }
 
+// ------------------------------------------------------------------ exact integrals (flux budgets)
+
+extern "C" int fcx_sum_clear(fcx_exact_sum *s) {
+  if (!s) return fail(FCX_E_ARG, "fcx_sum_clear: NULL sum");
+  std::memset(s, 0, sizeof *s);
+  return FCX_OK;
+}
+
+// the CPU twin of field_sum_kernel: the same term, the same digits; carries every kExsumHostRun terms
+template <class S>
+static int sum_add_terms(const char *who, fcx_exact_sum *s, const S *x, const double *a, int64_t n) {
+  if (!s || n < 0 || (n > 0 && !x)) return fail(FCX_E_ARG, "%s: bad arguments", who);
+  exsum_normalise(s->limb);
+  for (int64_t j0 = 0; j0 < n; j0 += kExsumHostRun) {
+    const int64_t j1 = std::min(n, j0 + kExsumHostRun);
+    for (int64_t j = j0; j < j1; ++j) {
+      const double xj = (double)x[j];
+      const double t = a ? a[j] * xj : xj;  // one IEEE multiply (-ffp-contract=off)
+      uint64_t bits;
+      std::memcpy(&bits, &t, sizeof bits);
+      switch (exsum_class(bits)) {
+        case 0: ++s->n_terms; exsum_add_finite(s->limb, bits); break;
+        case 1: ++s->n_nan; break;
+        case 2: ++s->n_pinf; break;
+        default: ++s->n_ninf; break;
+      }
+    }
+    exsum_normalise(s->limb);
+  }
+  return FCX_OK;
+}
+
+extern "C" int fcx_sum_add_terms(fcx_exact_sum *s, const double *x, const double *a, int64_t n) {
+  return sum_add_terms("fcx_sum_add_terms", s, x, a, n);
+}
+
+extern "C" int fcx_sum_add_terms_f32(fcx_exact_sum *s, const float *x, const double *a, int64_t n) {
+  return sum_add_terms("fcx_sum_add_terms_f32", s, x, a, n);
+}
+
+extern "C" int fcx_sum_merge(fcx_exact_sum *into, const fcx_exact_sum *other) {
+  if (!into) return fail(FCX_E_ARG, "fcx_sum_merge: NULL sum");
+  exsum_normalise(into->limb);
+  if (!other) return FCX_OK;
+  fcx_exact_sum o = *other;  // (other may be into)
+  exsum_normalise(o.limb);   // a raw sum of 2^30 canonical sums stays below 2^62 here
+  for (int k = 0; k < kExsumLimbs; ++k) into->limb[k] += o.limb[k];
+  exsum_normalise(into->limb);
+  into->n_terms += o.n_terms, into->n_nan += o.n_nan, into->n_pinf += o.n_pinf, into->n_ninf += o.n_ninf;
+  return FCX_OK;
+}
+
+extern "C" int fcx_sum_value(const fcx_exact_sum *s, double *value) {
+  if (!s || !value) return fail(FCX_E_ARG, "fcx_sum_value: bad arguments");
+  if (s->n_nan > 0 || (s->n_pinf > 0 && s->n_ninf > 0)) {
+    *value = std::nan("");
+  } else if (s->n_pinf > 0 || s->n_ninf > 0) {
+    *value = s->n_pinf > 0 ? HUGE_VAL : -HUGE_VAL;
+  } else {
+    fcx_exact_sum c = *s;
+    exsum_normalise(c.limb);
+    *value = exsum_round(c.limb);
+  }
+  return FCX_OK;
+}
+
+static const char *area_grid_name(int k) {
+  static const char *const names[4] = {"exchange grid t", "exchange grid u", "exchange grid v", "the atmosphere cells"};
+  return names[k];
+}
+
+// areas k (0..2 an exchange grid, 3 the atmosphere cells), the first `keep` of the caller's values
+static int set_areas(fcx_engine *e, const char *who, int k, const double *area, int64_t n, int64_t keep) {
+  if (n < keep || (keep > 0 && !area))
+    return fail(FCX_E_ARG, "%s: %lld areas, %s has %lld cells", who, (long long)n, area_grid_name(k), (long long)keep);
+  for (int64_t j = 0; j < keep; ++j)
+    if (!std::isfinite(area[j])) return fail(FCX_E_ARG, "%s: the area of cell %lld of %s is not finite", who, (long long)j, area_grid_name(k));
+  fcx_engine::Areas &ar = e->areas[k];
+  ar.host.assign(area, area + std::max<int64_t>(keep, 0));
+  ar.set = true;
+  return FCX_OK;
+}
+
+extern "C" int fcx_set_areas(fcx_engine *e, int grid, const double *area, int64_t n) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (grid < 1 || grid > 3) return fail(FCX_E_ARG, "fcx_set_areas: grid %d unknown (1..3)", grid);
+  return set_areas(e, "fcx_set_areas", grid - 1, area, n, e->n[grid - 1]);
+}
+
+extern "C" int fcx_set_atmos_areas(fcx_engine *e, const double *area, int64_t n_atmos) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (e->n_atmos < 0) return fail(FCX_E_STATE, "fcx_set_atmos_areas: no atmosphere map (fcx_set_atmos_map)");
+  if (n_atmos != e->n_atmos)
+    return fail(FCX_E_ARG, "fcx_set_atmos_areas: %lld areas, the map has %lld atmosphere cells", (long long)n_atmos,
+                (long long)e->n_atmos);
+  return set_areas(e, "fcx_set_atmos_areas", 3, area, n_atmos, n_atmos);
+}
+
+// the device copy of areas k, uploaded when the caller's values are newer; FCX_E_STATE without any
+static int areas_on_device(fcx_engine *e, const char *who, int k, const double **dev) {
+  fcx_engine::Areas &ar = e->areas[k];
+  if (!ar.set) return fail(FCX_E_STATE, "%s: weighted, but no areas were set for %s", who, area_grid_name(k));
+  if (!ar.dev || !ar.host.empty()) {
+    HIP_TRY(hipStreamSynchronize(e->stream));  // (a replaced array: no launch still reads the old one)
+    if (int r = ar.dev.upload(ar.host)) return r;
+    std::vector<double>().swap(ar.host);
+  }
+  *dev = ar.dev;
+  return FCX_OK;
+}
+
+// the integral launches' scratch, as range_scratch keeps the range launches'
+static int sum_scratch(fcx_engine *e, size_t fields) {
+  if (!e->sum_partial) HIP_TRY(e->sum_partial.alloc((size_t)kRangePartials * kSumWords * sizeof(int64_t)));
+  if (fields <= e->sum_cap) return FCX_OK;
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  const size_t cap = (fields + 15) / 16 * 16;
+  if (e->sum_host) (void)hipHostFree(e->sum_host);
+  e->sum_host = nullptr;
+  e->sum_cap = 0;
+  HIP_TRY(hipHostMalloc((void **)&e->sum_host, cap * sizeof(fcx_exact_sum), kHostPinFlags));
+  HIP_TRY(e->sum_out.alloc(cap * sizeof(fcx_exact_sum)));
+  e->sum_cap = cap;
+  return FCX_OK;
+}
+
+// one field of an integral launch: a range item, or a wave-uniform constant's value
+struct SumItem {
+  RangeItem it;
+  bool uniform;
+  double cval;
+  int area;  // which areas weigh it
+};
+
+// the launches of `items`, the copy of their results and the wait; results in e->sum_host[0..)
+static int run_sums(fcx_engine *e, const char *who, const std::vector<SumItem> &items, bool weighted) {
+  if (items.empty()) return FCX_OK;
+  const double *area[4] = {nullptr, nullptr, nullptr, nullptr};
+  if (weighted)
+    for (const SumItem &s : items)
+      if (!area[s.area])
+        if (int r = areas_on_device(e, who, s.area, &area[s.area])) return r;
+  if (int r = sum_scratch(e, items.size())) return r;
+  for (size_t k0 = 0; k0 < items.size(); k0 += kMaxRangeFields) {
+    SumArgs a{};
+    a.f32 = e->f32 ? 1 : 0;
+    a.weighted = weighted ? 1 : 0;
+    a.baseline = e->sum_baseline ? 1 : 0;
+    a.partial = e->sum_partial;
+    a.out = e->sum_out.p + k0;
+    for (size_t k = k0; k < std::min(items.size(), k0 + kMaxRangeFields); ++k) {
+      const SumItem &s = items[k];
+      a.f[a.nf++] = SumField{RangeField{s.uniform ? nullptr : s.it.p, s.it.n, s.it.tpad, s.it.stride, 0},
+                             weighted ? area[s.area] : nullptr, s.cval, s.uniform ? 1 : 0, 0};
+    }
+    const int r = launch_field_sums(a, e->stream);
+    if (r) return fail(FCX_E_HIP, "field integral launch: %s", hipGetErrorString((hipError_t)r));
+  }
+  HIP_TRY(hipMemcpyAsync(e->sum_host, e->sum_out.p, items.size() * sizeof(fcx_exact_sum), kD2H, e->stream));
+  HIP_TRY(hipStreamSynchronize(e->stream));
+  return FCX_OK;
+}
+
+extern "C" int fcx_field_integrals(fcx_engine *e, int32_t n, const int32_t *slots, int weighted, fcx_exact_sum *out) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (n < 0 || (n > 0 && (!slots || !out)) || weighted < 0 || weighted > 1)
+    return fail(FCX_E_ARG, "fcx_field_integrals: bad arguments");
+  for (int32_t k = 0; k < n; ++k)
+    if (!slot_ok(slots[3 * k], slots[3 * k + 1], slots[3 * k + 2]))
+      return fail(FCX_E_ARG, "fcx_field_integrals: slot %d (%d,%d,%d) out of range", k, slots[3 * k], slots[3 * k + 1],
+                  slots[3 * k + 2]);
+  if (int r = check(e)) return r;
+  std::vector<SumItem> items;
+  for (int32_t k = 0; k < n; ++k) {
+    const int s = slots[3 * k], g = slots[3 * k + 1], v = slots[3 * k + 2];
+    const int b = e->buf(s, g, v);
+    if (b < 0)
+      return fail(FCX_E_ARG, "fcx_field_integrals: %s(%d,%s) is not bound", kVarNames[v - 1], s, grid_name(g));
+    if (int r = stale_check(e, b, "fcx_field_integrals")) return r;
+    if (weighted && !e->areas[g - 1].set)
+      return fail(FCX_E_STATE, "fcx_field_integrals: weighted, but no areas were set for %s", area_grid_name(g - 1));
+    const Buffer &bf = e->bufs[(size_t)b];
+    // a wave-uniform constant: the launch carries the value the kernels see, no array is filled
+    const bool uniform = bf.constant && bf.uniform && !bf.filled;
+    const double val = e->f32 ? (double)(float)bf.cval : bf.cval;
+    items.push_back(SumItem{RangeItem{bf.dev, e->n[g - 1], bf.external ? 0 : e->tpad, 1, 0, s, g, v}, uniform,
+                            uniform ? val : 0.0, g - 1});
+  }
+  if (int r = run_sums(e, "fcx_field_integrals", items, weighted != 0)) return r;
+  for (int32_t k = 0; k < n; ++k) out[k] = e->sum_host[k];
+  return FCX_OK;
+}
+
+extern "C" int fcx_atmos_integrals(fcx_engine *e, int phase, int weighted, int32_t cap, fcx_exact_sum *out,
+                                   int32_t *n_fields) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (!n_fields || cap < 0 || (cap > 0 && !out) || weighted < 0 || weighted > 1)
+    return fail(FCX_E_ARG, "fcx_atmos_integrals: bad arguments");
+  if (phase < 1 || phase > 3) return fail(FCX_E_ARG, "phase %d unknown", phase);
+  if (int r = check(e)) return r;
+  std::vector<SumItem> items;
+  for (size_t k = 0; k < e->atm_fields.size(); ++k)
+    if (e->atm_fields[k].phase & phase) items.push_back(SumItem{atmos_item(e, k), false, 0.0, 3});
+  *n_fields = (int32_t)items.size();
+  if ((int32_t)items.size() > cap)
+    return fail(FCX_E_ARG, "fcx_atmos_integrals: phase %d has %d atmosphere outputs, cap is %d", phase, (int)items.size(), cap);
+  if (int r = run_sums(e, "fcx_atmos_integrals", items, weighted != 0)) return r;
+  for (size_t k = 0; k < items.size(); ++k) out[k] = e->sum_host[k];
+  return FCX_OK;
+}
+
 // The buffers a whole-phase run of `phase` reads (ins: every buffer a plan of the phase reads
 // without producing it, the received fields' arrays and the filled constants it streams included)
 // and stores (outs: the plans' writes -- dropped stores are not among them -- and the regrid
@@ -4876,6 +5103,10 @@ extern "C" int fcx_set_option(fcx_engine *e, int option, int64_t value) {
       if (e->committed) return fail(FCX_E_STATE, "check_finite is applied at fcx_commit");
       if (value < 0 || value > 3) return fail(FCX_E_ARG, "check_finite: bit 0 the outputs, bit 1 the inputs (0..3)");
       e->check_finite = (int)value;
+      return FCX_OK;
+    case FCX_OPT_SUM_BASELINE:
+      if (value < 0 || value > 1) return fail(FCX_E_ARG, "sum_baseline: 0 register windows, 1 every term through LDS");
+      e->sum_baseline = value != 0;
       return FCX_OK;
     case FCX_OPT_TILED_LAYOUT:
       if (e->committed) return fail(FCX_E_STATE, "tiled_layout is applied at fcx_commit");

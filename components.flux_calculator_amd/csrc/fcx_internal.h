@@ -505,4 +505,31 @@ struct RangeArgs {
 };
 int launch_field_ranges(RangeArgs a, void *stream);
 
+// Exact field sums (fcx_field_integrals, fcx_atmos_integrals; fcx_integrals.hip, fcx_exactsum.h):
+// the range launches' descriptor and addressing rule, plus per field the areas (cell j's weight
+// is area[j]: contiguous, never tile-blocked, a 16-B aligned allocation of the engine's; nullptr
+// when the launch is unweighted) and, for a wave-uniform constant, the value in place of an
+// array (uniform: r.p is not read, every cell j < r.n holds cval).  field_sum_kernel stores one
+// canonical 72-word partial (68 limbs, 4 counts: an fcx_exact_sum) per (field, block) into
+// `partial` ([nf][blocks] of kRangePartials, 1.1 MiB of scratch), field_sum_finish_kernel folds
+// them into out[f].
+constexpr int kSumWords = FCX_SUM_LIMBS + 4;
+struct SumField {
+  RangeField r;
+  const double *area;
+  double cval;
+  int32_t uniform;
+  int32_t pad;
+};
+struct SumArgs {
+  int32_t nf;
+  int32_t f32;       // float fields (widened to double, exactly)
+  int32_t weighted;  // every field's area is set
+  int32_t baseline;  // measurement: every term through the LDS accumulator, no register window
+  SumField f[kMaxRangeFields];
+  int64_t *partial;
+  fcx_exact_sum *out;  // [nf], device memory
+};
+int launch_field_sums(SumArgs a, void *stream);
+
 }  // namespace fcx

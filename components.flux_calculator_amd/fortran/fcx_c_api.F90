@@ -28,7 +28,7 @@ MODULE fcx_c_api
                                FCX_OPT_ATMOS_HALO = 17, FCX_OPT_DEFERRED_SCATTER = 18, &
                                FCX_OPT_LIB_SPANS = 19, FCX_OPT_ATM_RECORDS = 21, &
                                FCX_OPT_F32_MATH = 22, FCX_OPT_CHECK_FINITE = 23, &
-                               FCX_OPT_CR_MATH = 24
+                               FCX_OPT_CR_MATH = 24, FCX_OPT_SUM_BASELINE = 25
   ! the non-finite guard (FCX_OPT_CHECK_FINITE) found a NaN or an Inf
   INTEGER(c_int), PARAMETER :: FCX_E_NONFINITE = 7
   ! struct fcx_field_range: min / max over the cells that are not NaN, the NaN and Inf counts, the
@@ -36,6 +36,15 @@ MODULE fcx_c_api
   TYPE, BIND(C) :: fcx_field_range
     REAL(c_double) :: vmin, vmax
     INTEGER(c_int64_t) :: n_nan, n_inf, first_bad
+  END TYPE
+  ! struct fcx_exact_sum (576 B): an exact sum of doubles, value = sum_k limb(k) * 2**(32 k - 1088)
+  ! (k from 0), and the counts of the finite terms in it and of the NaN / +Inf / -Inf terms left
+  ! out.  Canonical sums of several ranks add as 72 INTEGER(8) under MPI_SUM; fcx_sum_merge of the
+  ! result normalises it, fcx_sum_value rounds it once.
+  INTEGER, PARAMETER :: FCX_SUM_LIMBS = 68
+  TYPE, BIND(C) :: fcx_exact_sum
+    INTEGER(c_int64_t) :: limb(FCX_SUM_LIMBS)
+    INTEGER(c_int64_t) :: n_terms, n_nan, n_pinf, n_ninf
   END TYPE
   ! retired in version 3: accepted by fcx_set_option and ignored
   INTEGER(c_int), PARAMETER :: FCX_OPT_PIN_HOST = 6, FCX_OPT_CARRY_HANDOFF = 14
@@ -432,6 +441,76 @@ MODULE fcx_c_api
       TYPE(fcx_field_range), DIMENSION(*), INTENT(OUT) :: ranges
       INTEGER(c_int32_t), INTENT(OUT) :: n_fields
       INTEGER(c_int) :: fcx_atmos_ranges
+    END FUNCTION
+    ! exact sums on the host (no engine, no GPU)
+    FUNCTION fcx_sum_clear(s) BIND(C, name='fcx_sum_clear')
+      IMPORT :: c_int, fcx_exact_sum
+      TYPE(fcx_exact_sum), INTENT(OUT) :: s
+      INTEGER(c_int) :: fcx_sum_clear
+    END FUNCTION
+    ! the terms x(1:n), or area(j) * x(j) when area is not c_null_ptr, added to s
+    FUNCTION fcx_sum_add_terms(s, x, area, n) BIND(C, name='fcx_sum_add_terms')
+      IMPORT :: c_int, c_int64_t, c_ptr, fcx_exact_sum
+      TYPE(fcx_exact_sum), INTENT(INOUT) :: s
+      TYPE(c_ptr), VALUE :: x, area
+      INTEGER(c_int64_t), VALUE :: n
+      INTEGER(c_int) :: fcx_sum_add_terms
+    END FUNCTION
+    FUNCTION fcx_sum_add_terms_f32(s, x, area, n) BIND(C, name='fcx_sum_add_terms_f32')
+      IMPORT :: c_int, c_int64_t, c_ptr, fcx_exact_sum
+      TYPE(fcx_exact_sum), INTENT(INOUT) :: s
+      TYPE(c_ptr), VALUE :: x, area
+      INTEGER(c_int64_t), VALUE :: n
+      INTEGER(c_int) :: fcx_sum_add_terms_f32
+    END FUNCTION
+    ! into = into + other, normalised; other may be the raw MPI_SUM of canonical sums
+    FUNCTION fcx_sum_merge(into, other) BIND(C, name='fcx_sum_merge')
+      IMPORT :: c_int, fcx_exact_sum
+      TYPE(fcx_exact_sum), INTENT(INOUT) :: into
+      TYPE(fcx_exact_sum), INTENT(IN) :: other
+      INTEGER(c_int) :: fcx_sum_merge
+    END FUNCTION
+    FUNCTION fcx_sum_value(s, value) BIND(C, name='fcx_sum_value')
+      IMPORT :: c_int, c_double, fcx_exact_sum
+      TYPE(fcx_exact_sum), INTENT(IN) :: s
+      REAL(c_double), INTENT(OUT) :: value
+      INTEGER(c_int) :: fcx_sum_value
+    END FUNCTION
+    ! cell areas of exchange grid 1..3 (n >= grid_size doubles), of the local atmosphere cells
+    FUNCTION fcx_set_areas(engine, grid, area, n) BIND(C, name='fcx_set_areas')
+      IMPORT :: c_int, c_int64_t, c_double, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int), VALUE :: grid
+      REAL(c_double), DIMENSION(*), INTENT(IN) :: area
+      INTEGER(c_int64_t), VALUE :: n
+      INTEGER(c_int) :: fcx_set_areas
+    END FUNCTION
+    FUNCTION fcx_set_atmos_areas(engine, area, n_atmos) BIND(C, name='fcx_set_atmos_areas')
+      IMPORT :: c_int, c_int64_t, c_double, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      REAL(c_double), DIMENSION(*), INTENT(IN) :: area
+      INTEGER(c_int64_t), VALUE :: n_atmos
+      INTEGER(c_int) :: fcx_set_atmos_areas
+    END FUNCTION
+    ! exact (weighted = 1: area-weighted) sums of n slots, slots(3, n), on the device
+    FUNCTION fcx_field_integrals(engine, n, slots, weighted, sums) BIND(C, name='fcx_field_integrals')
+      IMPORT :: c_int, c_int32_t, c_ptr, fcx_exact_sum
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int32_t), VALUE :: n
+      INTEGER(c_int32_t), DIMENSION(*), INTENT(IN) :: slots
+      INTEGER(c_int), VALUE :: weighted
+      TYPE(fcx_exact_sum), DIMENSION(*), INTENT(OUT) :: sums
+      INTEGER(c_int) :: fcx_field_integrals
+    END FUNCTION
+    FUNCTION fcx_atmos_integrals(engine, phase, weighted, cap, sums, n_fields) &
+        BIND(C, name='fcx_atmos_integrals')
+      IMPORT :: c_int, c_int32_t, c_ptr, fcx_exact_sum
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int), VALUE :: phase, weighted
+      INTEGER(c_int32_t), VALUE :: cap
+      TYPE(fcx_exact_sum), DIMENSION(*), INTENT(OUT) :: sums
+      INTEGER(c_int32_t), INTENT(OUT) :: n_fields
+      INTEGER(c_int) :: fcx_atmos_integrals
     END FUNCTION
     ! what FCX_OPT_CHECK_FINITE checks after a run of the phase: slots(3, n), inputs first
     FUNCTION fcx_check_fields(engine, phase, cap, slots, n) BIND(C, name='fcx_check_fields')

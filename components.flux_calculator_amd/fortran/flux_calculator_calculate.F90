@@ -54,6 +54,7 @@ MODULE flux_calculator_calculate
     PUBLIC fcx_select_outputs
     PUBLIC fcx_define_receive_map, fcx_declare_received
     PUBLIC fcx_check_finite, fcx_field_range_of
+    PUBLIC fcx_declare_areas, fcx_field_integral_of
 
     TYPE(c_ptr), SAVE :: engine = c_null_ptr
     ! What fcx_attach bound.  The reference subroutines take the bottom model, the type count,
@@ -440,6 +441,37 @@ CONTAINS
         vmax = REAL(r(1)%vmax, wp)
         n_bad = INT(r(1)%n_nan + r(1)%n_inf)
     END SUBROUTINE fcx_field_range_of
+
+    ! The cell areas of exchange grid which_grid for the flux budgets: grid_area as the host holds
+    ! it for oasis_write_area (flux_calculator.F90:791-793), this rank's window of it, at least
+    ! grid_size(which_grid) values.  Before or after fcx_commit_engine; again to replace them.
+    SUBROUTINE fcx_declare_areas(which_grid, area)
+        INTEGER,                INTENT(IN) :: which_grid
+        REAL(wp), DIMENSION(:), INTENT(IN) :: area
+        REAL(c_double), ALLOCATABLE :: a(:)
+        a = REAL(area, c_double)
+        CALL check(fcx_set_areas(engine, INT(which_grid, c_int), a, SIZE(a, KIND=c_int64_t)), 'fcx_set_areas')
+    END SUBROUTINE fcx_declare_areas
+
+    ! The integral of local_field(surface_type, which_grid)%var(my_idx) over the grid as the engine
+    ! holds it on the device: sum_j area(j) * field(j) (weighted) or sum_j field(j), exact and
+    ! rounded once -- the same bits whatever the decomposition.  value is this rank's; hosts that
+    ! want the global budget add the ranks' fcx_exact_sum with MPI_SUM (fcx_field_integrals,
+    ! fcx_sum_merge, fcx_sum_value of fcx_c_api).  Terms that are NaN or +-Inf are left out of the
+    ! sum and make value NaN or +-Inf, as fcx_sum_value defines it.
+    SUBROUTINE fcx_field_integral_of(surface_type, which_grid, my_idx, weighted, value)
+        INTEGER,  INTENT(IN)  :: surface_type, which_grid, my_idx
+        LOGICAL,  INTENT(IN)  :: weighted
+        REAL(wp), INTENT(OUT) :: value
+        INTEGER(c_int32_t) :: slot(3)
+        TYPE(fcx_exact_sum) :: s(1)
+        REAL(c_double) :: v
+        slot = [INT(surface_type, c_int32_t), INT(which_grid, c_int32_t), INT(my_idx, c_int32_t)]
+        CALL check(fcx_field_integrals(engine, 1_c_int32_t, slot, MERGE(1_c_int, 0_c_int, weighted), s), &
+                   'fcx_field_integrals')
+        CALL check(fcx_sum_value(s(1), v), 'fcx_sum_value')
+        value = REAL(v, wp)
+    END SUBROUTINE fcx_field_integral_of
 
     ! every plan the engine can launch audited on the host first (fcx_plan_check: a method
     ! that would read an input the set-up left unbound stops here with a named error, before

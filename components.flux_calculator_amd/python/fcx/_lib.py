@@ -24,7 +24,9 @@ FCX_PRECISION_F32 = 1
 FCX_OPT_F32_MATH = 22  # an fp32 engine's fluxes computed in double (fcx_set_option)
 FCX_OPT_CHECK_FINITE = 23  # the non-finite guard: bit 0 the phase's outputs, bit 1 its inputs
 FCX_OPT_CR_MATH = 24  # an fp64 engine's exp and Exner power correctly rounded (fcx_set_option)
+FCX_OPT_SUM_BASELINE = 25  # measurement: the integral launches without the lanes' register windows
 FCX_E_NONFINITE = 7
+FCX_SUM_LIMBS = 68
 FCX_COMM_ID_BYTES = 128
 FCX_OUT_HOST = 0
 FCX_OUT_DEVICE = 1
@@ -44,6 +46,14 @@ class FieldRangeC(_c.Structure):
     _fields_ = [("min", _c.c_double), ("max", _c.c_double), ("n_nan", _I64), ("n_inf", _I64),
                 ("first_bad", _I64)]
 
+
+class ExactSumC(_c.Structure):
+    """struct fcx_exact_sum (576 B): value = sum_k limb[k] * 2**(32 k - 1088), and the counts"""
+    _fields_ = [("limb", _I64 * FCX_SUM_LIMBS), ("n_terms", _I64), ("n_nan", _I64), ("n_pinf", _I64),
+                ("n_ninf", _I64)]
+
+
+_SP = _c.POINTER(ExactSumC)
 
 SIGNATURES = [
     ("fcx_last_error", _c.c_char_p, []),
@@ -131,6 +141,15 @@ SIGNATURES = [
     ("fcx_check_fields", _I, [_P, _I, _I32, _P, _c.POINTER(_I32)]),
     ("fcx_check_result", _I, [_P, _c.POINTER(_I32), _c.POINTER(_I32), _c.POINTER(_I32), _c.POINTER(_I32),
                               _c.POINTER(_I64), _DP]),
+    ("fcx_sum_clear", _I, [_SP]),
+    ("fcx_sum_add_terms", _I, [_SP, _P, _P, _I64]),
+    ("fcx_sum_add_terms_f32", _I, [_SP, _P, _P, _I64]),
+    ("fcx_sum_merge", _I, [_SP, _SP]),
+    ("fcx_sum_value", _I, [_SP, _DP]),
+    ("fcx_set_areas", _I, [_P, _I, _P, _I64]),
+    ("fcx_set_atmos_areas", _I, [_P, _P, _I64]),
+    ("fcx_field_integrals", _I, [_P, _I32, _P, _I, _SP]),
+    ("fcx_atmos_integrals", _I, [_P, _I, _I, _I32, _SP, _c.POINTER(_I32)]),
 ]
 
 

@@ -65,9 +65,31 @@ def _log_ranges(setup, engine, early, current_time, log):
         log(f"  {what}  {f.name} at runtime={current_time} seconds: range = {lo!r} {hi!r}")
 
 
-def coupling_step(setup, engine, coupler, current_time, log=None):
+def _log_budgets(setup, engine, early, phase, current_time, budgets):
+    """A phase's flux budgets: name and area-weighted integral of every sent field, exact on the
+    device (ONE fcx_field_integrals call; the engine needs the grids' areas, Engine.set_areas).
+    Where the engine accumulates the field onto the atmosphere grid and holds the atmosphere
+    cells' areas (Engine.set_atmos_areas), the line also gives the atmosphere-side integral and
+    the difference of the two exact sums, rounded once: what the step failed to conserve."""
+    sent = setup.fields_in_put_order(setup.output_field, early)
+    if not sent:
+        return
+    sums = list(engine.field_integrals([f.slot for f in sent]))
+    twins = engine.atmos_twins(phase)
+    atmo = dict(zip(twins, engine.atmos_integrals(phase))) if twins else {}
+    for f, sx in zip(sent, sums):
+        line = f"  budget  {f.name} at runtime={current_time} seconds: integral = {sx.value!r}"
+        sa = atmo.get(tuple(f.slot))
+        if sa is not None:
+            line += f" atmosphere = {sa.value!r} difference = {(sx + (-sa)).value!r}"
+        budgets(line)
+
+
+def coupling_step(setup, engine, coupler, current_time, log=None, budgets=None):
     """log: a callable taking one line; with nml["verbosity_level"] at DEBUG every phase then
-    reports the ranges of its received and sent fields (_log_ranges).  None: no range call."""
+    reports the ranges of its received and sent fields (_log_ranges).  None: no range call.
+    budgets: a callable taking one line; every phase then reports the area-weighted integral of
+    each sent field after its step (_log_budgets).  None: no integral call."""
     lf = setup.local_field
     debug = log is not None and setup.nml.get("verbosity_level", 1) >= VERBOSITY_LEVEL_DEBUG
     for early, phase in ((True, PHASE_EARLY), (False, PHASE_NORMAL)):
@@ -83,17 +105,19 @@ def coupling_step(setup, engine, coupler, current_time, log=None):
         engine.step(phase, current_time)
         if debug:
             _log_ranges(setup, engine, early, current_time, log)
+        if budgets is not None:
+            _log_budgets(setup, engine, early, phase, current_time, budgets)
         for f in setup.fields_in_put_order(setup.output_field, early):
             coupler.put(f.name, current_time, lf.field[f.slot])
 
 
-def run(setup, engine, coupler, num_timesteps=None, timestep=None, log=None):
+def run(setup, engine, coupler, num_timesteps=None, timestep=None, log=None, budgets=None):
     """DO n_timestep = 1, num_timesteps; current_time = (n_timestep - 1) * timestep.
-    log: see coupling_step."""
+    log, budgets: see coupling_step."""
     n = setup.nml["num_timesteps"] if num_timesteps is None else num_timesteps
     dt = setup.nml["timestep"] if timestep is None else timestep
     for k in range(1, n + 1):
-        coupling_step(setup, engine, coupler, (k - 1) * dt, log=log)
+        coupling_step(setup, engine, coupler, (k - 1) * dt, log=log, budgets=budgets)
 
 
 __all__ = ["coupling_step", "run"]

@@ -19,6 +19,99 @@ def _ranges(buf, n):
     return [FieldRange(r.min, r.max, r.n_nan, r.n_inf, r.first_bad) for r in buf[:n]]
 
 
+class ExactSum:
+    """struct fcx_exact_sum as a value: an exact sum of doubles (a fixed-point long accumulator of
+    68 limbs, value = sum_k limbs[k] * 2**(32 k - 1088)) with the counts of the terms that are in
+    it (n_terms) and of those left out (n_nan, n_pinf, n_ninf).  Always canonical, so two sums are
+    equal iff bytes(a) == bytes(b).  a + b merges (fcx_sum_merge); .value rounds once
+    (fcx_sum_value).  Needs neither a GPU nor an engine."""
+
+    __slots__ = ("c",)
+
+    def __init__(self, c=None):
+        self.c = _lib.ExactSumC()
+        if c is not None:
+            ctypes.memmove(ctypes.byref(self.c), ctypes.byref(c), ctypes.sizeof(_lib.ExactSumC))
+
+    @classmethod
+    def of(cls, x, area=None):
+        """The host twin of the device kernel: the exact sum of x (float64 or float32), or of
+        the IEEE products area[j] * x[j]."""
+        return cls().add_terms(x, area)
+
+    def add_terms(self, x, area=None):
+        x = np.ascontiguousarray(x)
+        if x.dtype not in (np.float64, np.float32) or x.ndim != 1:
+            raise TypeError("ExactSum: a 1-D float64 or float32 array")
+        a = None
+        if area is not None:
+            a = np.ascontiguousarray(area, dtype=np.float64)
+            if a.shape != x.shape:
+                raise ValueError("ExactSum: one area per term")
+        fn = _lib.load().fcx_sum_add_terms_f32 if x.dtype == np.float32 else _lib.load().fcx_sum_add_terms
+        _lib.check(fn(self.c, ctypes.c_void_p(x.ctypes.data), ctypes.c_void_p(a.ctypes.data) if a is not None else None,
+                      x.shape[0]))
+        return self
+
+    @classmethod
+    def from_raw(cls, words):
+        """72 int64 words (68 limbs, 4 counts), e.g. the MPI_SUM of the ranks' canonical sums,
+        normalised once."""
+        w = np.ascontiguousarray(words, dtype=np.int64).reshape(-1)
+        if w.shape[0] != _lib.FCX_SUM_LIMBS + 4:
+            raise ValueError("ExactSum.from_raw: 72 int64 words")
+        raw = _lib.ExactSumC.from_buffer_copy(w.tobytes())
+        out = cls()
+        _lib.check(_lib.load().fcx_sum_merge(out.c, raw))
+        return out
+
+    def words(self):
+        """the 72 int64 words of the struct (what a host adds across ranks)"""
+        return np.frombuffer(bytes(self), dtype=np.int64).copy()
+
+    @property
+    def value(self):
+        v = ctypes.c_double()
+        _lib.check(_lib.load().fcx_sum_value(self.c, ctypes.byref(v)))
+        return v.value
+
+    @property
+    def limbs(self):
+        return list(self.c.limb)
+
+    n_terms = property(lambda self: self.c.n_terms)
+    n_nan = property(lambda self: self.c.n_nan)
+    n_pinf = property(lambda self: self.c.n_pinf)
+    n_ninf = property(lambda self: self.c.n_ninf)
+
+    def __neg__(self):
+        """the sum of the negated terms (an infinity's count changes sides)"""
+        w = self.words()
+        w[:_lib.FCX_SUM_LIMBS] = -w[:_lib.FCX_SUM_LIMBS]
+        w[-2], w[-1] = w[-1], w[-2]
+        return ExactSum.from_raw(w)
+
+    def __add__(self, other):
+        if not isinstance(other, ExactSum):
+            return NotImplemented
+        out = ExactSum(self.c)
+        _lib.check(_lib.load().fcx_sum_merge(out.c, other.c))
+        return out
+
+    def __bytes__(self):
+        return ctypes.string_at(ctypes.byref(self.c), ctypes.sizeof(_lib.ExactSumC))
+
+    def __eq__(self, other):
+        return isinstance(other, ExactSum) and bytes(self) == bytes(other)
+
+    def __hash__(self):
+        return hash(bytes(self))
+
+    def __repr__(self):
+        return (f"ExactSum(value={self.value!r}, n_terms={self.n_terms}, n_nan={self.n_nan}, "
+                f"n_pinf={self.n_pinf}, n_ninf={self.n_ninf})")
+
+
 class Engine:
     """Binds every slot of a LocalFields to a new libfcx engine and commits it.
 
@@ -64,6 +157,10 @@ class Engine:
         self.T = int(num_surface_types)
         self.methods = {k: list(v) for k, v in methods.items()}
         self._keep = []
+        # the accumulated fields, (phase, surface_type, grid, name) in registration order (the
+        # order of atmos_integrals), and whether their cells' areas were set
+        self.atmos_fields = [(int(p), int(s), int(g), name) for p, s, g, name, _ in (atmos or {}).get("fields", ())]
+        self.atmos_areas_set = False
         h = ctypes.c_void_p()
         gs = (ctypes.c_int32 * 3)(*lf.grid_size)
         _lib.check(self.lib.fcx_create(device, self.T, gs, ctypes.byref(h)))
@@ -256,7 +353,7 @@ class Engine:
                "timing": 10, "tiled_layout": 11, "remap_pack": 13, "host_staging": 15, "host_threads": 16,
                "atmos_halo": 17, "deferred_scatter": 18, "lib_spans": 19, "atm_records": 21,
                "f32_math": _lib.FCX_OPT_F32_MATH, "check_finite": _lib.FCX_OPT_CHECK_FINITE,
-               "cr_math": _lib.FCX_OPT_CR_MATH}
+               "cr_math": _lib.FCX_OPT_CR_MATH, "sum_baseline": _lib.FCX_OPT_SUM_BASELINE}
 
     def run_atmos(self, phase=PHASE_ALL):
         _lib.check(self.lib.fcx_run_atmos(self.h, phase))
@@ -438,6 +535,53 @@ class Engine:
         return {"is_atmos": bool(a.value), "surface_type": s.value, "grid": g.value, "var": v.value,
                 "name": names.get(v.value), "cell": cell.value, "value": value.value}
 
+    # ---- exact integrals (flux budgets)
+    def set_areas(self, grid, area):
+        """fcx_set_areas: the cell areas of exchange grid `grid` (1..3), at least grid_size values;
+        before or after commit, and again to replace them."""
+        a = np.ascontiguousarray(area, dtype=np.float64).reshape(-1)
+        _lib.check(self.lib.fcx_set_areas(self.h, int(grid), ctypes.c_void_p(a.ctypes.data), a.shape[0]))
+
+    def set_atmos_areas(self, area):
+        """fcx_set_atmos_areas: the areas of the local atmosphere cells; 0.0 for a shared cell
+        this rank does not own (fcx.parallel.owned_atmos_mask)."""
+        a = np.ascontiguousarray(area, dtype=np.float64).reshape(-1)
+        _lib.check(self.lib.fcx_set_atmos_areas(self.h, ctypes.c_void_p(a.ctypes.data), a.shape[0]))
+        self.atmos_areas_set = True
+
+    def atmos_twins(self, phase=PHASE_ALL):
+        """The (surface_type, grid, name) slots whose accumulation onto the atmosphere grid
+        atmos_integrals(phase) integrates, in its order; none while no atmosphere areas are set."""
+        if not self.atmos_areas_set:
+            return []
+        return [(s, g, name) for p, s, g, name in self.atmos_fields if p & int(phase)]
+
+    def field_integrals(self, slots, weighted=True):
+        """fcx_field_integrals: an ExactSum per (surface_type, grid, name) of `slots`, in request
+        order: the exact sum of the device buffer behind each slot, its terms multiplied by the
+        grid's areas when weighted.  Waits for the engine's stream."""
+        slots = list(slots)
+        ids = np.array([(int(s), int(g), IDX[name] if isinstance(name, str) else int(name)) for s, g, name in slots],
+                       dtype=np.int32).reshape(-1)
+        out = (_lib.ExactSumC * max(len(slots), 1))()
+        _lib.check(self.lib.fcx_field_integrals(self.h, len(slots), ctypes.c_void_p(ids.ctypes.data),
+                                                1 if weighted else 0, out))
+        return [ExactSum(c) for c in out[:len(slots)]]
+
+    def atmos_integrals(self, phase=PHASE_ALL, weighted=True):
+        """fcx_atmos_integrals: an ExactSum per atmosphere output of the phase, in registration
+        order, read from the device arrays or records as they are."""
+        cap = 64
+        while True:
+            out = (_lib.ExactSumC * cap)()
+            n = ctypes.c_int32()
+            rc = self.lib.fcx_atmos_integrals(self.h, int(phase), 1 if weighted else 0, cap, out, ctypes.byref(n))
+            if rc == 1 and n.value > cap:
+                cap = n.value
+                continue
+            _lib.check(rc)
+            return [ExactSum(c) for c in out[:n.value]]
+
     def close(self):
         if self.h is not None:
             self.lib.fcx_destroy(self.h)
@@ -476,4 +620,4 @@ def current_month(init_date, seconds):
     return m.value
 
 
-__all__ = ["Engine", "FieldRange", "run_group", "current_month", "PHASE_EARLY", "PHASE_NORMAL", "PHASE_ALL"]
+__all__ = ["Engine", "ExactSum", "FieldRange", "run_group", "current_month", "PHASE_EARLY", "PHASE_NORMAL", "PHASE_ALL"]

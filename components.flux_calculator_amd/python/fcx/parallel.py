@@ -147,6 +147,18 @@ def local_atmos(amap: AtmosMap, rank, nranks, offset=None, size=None, right_slot
                       max(nranks - 1, 0))
 
 
+def owned_atmos_mask(la: LocalAtmos):
+    """1.0 for the local atmosphere cells this rank owns, 0.0 for the one it shares with a lower
+    rank: a shared cell belongs to the lowest rank holding part of it, i.e. a rank owns its first
+    cell unless that cell began before its range (left >= 0).  A rank multiplies its atmosphere
+    areas by this mask (Engine.set_atmos_areas), so that a shared cell counts once when the
+    ranks' integrals are added."""
+    mask = np.ones(la.n_atmos)
+    if la.n_atmos > 0 and la.left >= 0:
+        mask[0] = 0.0
+    return mask
+
+
 def pack_boundaries(la: LocalAtmos, partial_fields, stride):
     """CPU form of the engine's boundary write: [n_boundaries][stride] with this rank's partial
     sums of its shared first/last atmosphere cells (fields in columns), zero elsewhere."""

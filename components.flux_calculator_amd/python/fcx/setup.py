@@ -449,7 +449,7 @@ class FluxCalculatorSetup:
         return out
 
     def engine(self, corrections=None, regrid=None, select_outputs=False, receive_maps=None, check_finite=0,
-               **kw):
+               areas=None, **kw):
         """An fcx.Engine over the set-up's local_field (methods, averages, put_to).
         select_outputs: the unsent outputs are declared FCX_OUT_UNREAD (fcx_set_output_use), so
         they are neither downloaded nor, where nothing else reads them, stored.
@@ -458,7 +458,10 @@ class FluxCalculatorSetup:
         to the exchange grid by the engine (received()); fcx.driver hands the coupler the source
         arrays.  Without it nothing changes.
         check_finite: the non-finite guard (FCX_OPT_CHECK_FINITE): 1 every phase's outputs, 3 its
-        inputs too; a step that finds a NaN or an Inf raises fcx._lib.NonFiniteError."""
+        inputs too; a step that finds a NaN or an Inf raises fcx._lib.NonFiniteError.
+        areas: {which_grid (1..3, or "atmos"): cell areas} for the flux budgets (Engine.set_areas,
+        set_atmos_areas; fcx.driver's budgets lines).  An entry is this rank's array, or the dict
+        fcx.io.read_scrip_grid returns, whose global "area" is cut to the rank's window."""
         from . import _lib
         from .engine import Engine
 
@@ -472,8 +475,20 @@ class FluxCalculatorSetup:
             use = {slot: _lib.FCX_OUT_UNREAD for slot in self.unsent_outputs()}
             use.update(kw.pop("output_use", None) or {})
             kw["output_use"] = use
-        return Engine(self.local_field, self._T, self.methods, corrections=corrections,
-                      averages=self.averages(), regrid=regrid, **kw)
+        eng = Engine(self.local_field, self._T, self.methods, corrections=corrections,
+                     averages=self.averages(), regrid=regrid, **kw)
+        try:
+            for g, a in (areas or {}).items():
+                if isinstance(a, dict):
+                    a = a["area"][a.get("grid_offset", 0): a.get("grid_offset", 0) + a["grid_size"]]
+                if g == "atmos":
+                    eng.set_atmos_areas(a)
+                else:
+                    eng.set_areas(int(g), a)
+        except Exception:
+            eng.close()
+            raise
+        return eng
 
 
 def setup_from_namelist(path_or_text, mype=0, grid_size=None, **kw):

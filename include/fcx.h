@@ -427,6 +427,78 @@ int fcx_check_fields(fcx_engine *e, int phase, int32_t cap, int32_t *slots, int3
 int fcx_check_result(const fcx_engine *e, int32_t *is_atmos, int32_t *surface_type, int32_t *grid,
                      int32_t *var, int64_t *cell, double *value);
 
+/* ---- exact (area-weighted) field integrals: flux budgets ----
+ * How much heat, water or momentum crossed the surface in a step is sum_j A_j F_j over a grid, and
+ * a step is conservative when that sum over the exchange grid equals the one over the atmosphere
+ * grid.  Most fields never reach host memory, so the sum runs on the device; and because a budget
+ * is a cancelling sum that must not depend on block counts, tile order or the number of ranks, it
+ * is EXACT: a fixed-point long accumulator whose partial results add associatively, rounded once
+ * when a double is asked for.  The same bits for 1 rank or 8, for tile-blocked or contiguous
+ * mirrors, for any grid.
+ *
+ * The terms of field x over the cells j < n (n: the slot's grid size), fp64 arithmetic, no FMA:
+ *   unweighted  t_j = x_j;   weighted  t_j = fl(a_j * x_j), one IEEE double multiply.
+ * An fp32 engine's x_j is widened to double first (exactly); areas are always fp64.  The integral
+ * is sum_j t_j without any rounding.  A non-finite term (a NaN, +-Inf, a product that overflowed)
+ * never enters the limbs; it is counted.  Zeros of either sign contribute nothing; an empty or
+ * fully cancelling sum has the value +0.0.
+ *
+ *   value = sum_k limb[k] * 2^(32 k - 1088).  A finite double +-m * 2^q (m < 2^53, q >= -1074) lands
+ *   at bit p = q + 1088, in limbs p >> 5 .. (p >> 5) + 2, as the three 32-bit digits of
+ *   m << (p & 31).  Limbs 0..66 cover every double (DBL_MAX: limbs 64, 65; the smallest denormal:
+ *   limb[0] = 16384), limb 67 is carry headroom.
+ *   n_terms: the finite terms (zeros included); n_nan, n_pinf, n_ninf: the terms left out.  The
+ *   four counts add up to the cells summed.
+ * CANONICAL FORM -- what every entry point returns: limbs 0..66 in [0, 2^32), limb 67 signed (a
+ * negative value is the two's complement over the 68 limbs).  Every value has exactly one
+ * representation: two sums are equal iff their 576 bytes are.  Canonical sums of up to 2^30 ranks
+ * may be added limb by limb and count by count -- MPI_SUM on INTEGER(8), 72 of them -- and
+ * fcx_sum_merge(into, raw) of the result, once, gives the global sum.  No limb reaches 2^62 in
+ * magnitude at any point, on the device or the host (csrc/fcx_exactsum.h says where carries are
+ * propagated). */
+#define FCX_SUM_LIMBS 68
+typedef struct fcx_exact_sum {          /* 576 B */
+  int64_t limb[FCX_SUM_LIMBS];          /* value = sum_k limb[k] * 2^(32 k - 1088) */
+  int64_t n_terms, n_nan, n_pinf, n_ninf;
+} fcx_exact_sum;
+/* Host arithmetic (no GPU, no engine; the device kernels compile the same code).
+ * fcx_sum_clear: the empty sum.  fcx_sum_add_terms / _f32: the CPU twin of the kernel -- the terms
+ * of x[0..n) (a NULL: unweighted) added to *s, which is left canonical.  fcx_sum_merge: limbs and
+ * counts of `other` added to `into`, then normalised; `other` may be a raw limb-wise sum of up to
+ * 2^30 canonical sums, and other == NULL only normalises `into`.  fcx_sum_value: the sum rounded
+ * once, to nearest even; NaN when n_nan > 0 or both infinity counts are non-zero, +-Inf when one
+ * is, +-Inf when the exact value rounds beyond DBL_MAX (the limbs stay exact: a later merge can
+ * bring the value back). */
+int fcx_sum_clear(fcx_exact_sum *s);
+int fcx_sum_add_terms(fcx_exact_sum *s, const double *x, const double *a, int64_t n);
+int fcx_sum_add_terms_f32(fcx_exact_sum *s, const float *x, const double *a, int64_t n);
+int fcx_sum_merge(fcx_exact_sum *into, const fcx_exact_sum *other);
+int fcx_sum_value(const fcx_exact_sum *s, double *value);
+/* The cell areas of exchange grid `grid` (1..3: t, u, v), a host array of n >= grid_size doubles --
+ * the areas the reference hands to OASIS (flux_calculator.F90:791-793, oasis_write_area).  The
+ * engine keeps a contiguous device copy of the first grid_size values (never tile-blocked),
+ * uploaded once: the step's transports never see it and fcx_algorithmic_bytes does not count it.
+ * Before or after fcx_commit, and again to replace the array.  A non-finite area is FCX_E_ARG
+ * naming the cell; negative and zero areas are allowed. */
+int fcx_set_areas(fcx_engine *e, int grid, const double *area, int64_t n);
+/* ... and of the n_atmos local atmosphere cells (after fcx_set_atmos_map).  A rank passes 0.0 for
+ * an atmosphere cell it shares with a neighbour but does not own, so that a shared cell counts
+ * once across the ranks (fcx.parallel.owned_atmos_mask gives the rule: the lower rank owns). */
+int fcx_set_atmos_areas(fcx_engine *e, const double *area, int64_t n_atmos);
+/* The integrals of n slots, as fcx_field_ranges reads them (the same slot triples, argument checks,
+ * FCX_E_STATE before fcx_commit, stale FCX_OUT_UNREAD error; a slot is read where fcx_device_ptr
+ * points after a step), into out[k], canonical.  weighted 1: by the areas of the slot's grid
+ * (FCX_E_STATE naming the grid when none were set); 0: plain sums.  A wave-uniform constant has no
+ * array and gets none: the launch carries its value, and the result is that of an array holding
+ * it.  One streaming launch per 16 fields plus a one-block-per-field finishing launch, on the
+ * engine's stream, which the call waits for; the results travel through a page-locked buffer of
+ * the engine's own, 576 B per field. */
+int fcx_field_integrals(fcx_engine *e, int32_t n, const int32_t *slots, int weighted, fcx_exact_sum *out);
+/* ... of the atmosphere outputs of `phase`, as fcx_atmos_ranges reads them (pool slot, plain array
+ * or record column; no unpack launch), weighted by fcx_set_atmos_areas. */
+int fcx_atmos_integrals(fcx_engine *e, int phase, int weighted, int32_t cap, fcx_exact_sum *out,
+                        int32_t *n_fields);
+
 /* ---- exchange-grid -> atmosphere accumulation ----
  * What OASIS3-MCT does on oasis_put of the type-0 fields ('S A xxxx 00',
  * create_namcouple.F90:92-98): out[a] = sum_x weight[x] * field[x] over the local t-grid
@@ -690,6 +762,10 @@ enum fcx_option {
                                    without FCX_OPT_F32_MATH.  Applied at fcx_commit
                                    (FCX_E_STATE afterwards); other values are FCX_E_ARG; the
                                    environment variable FCX_CR_MATH (0, 1) sets the default  */
+  FCX_OPT_SUM_BASELINE = 25,    /* measurement: 1 = the integral launches add every term through
+                                   the block's LDS accumulator, without the lanes' register
+                                   windows (default 0).  The results are the same bits; only
+                                   the time differs (bench/integrals_ab.py).  At any time.   */
   FCX_OPT_TILED_LAYOUT = 11   /* engine-owned mirrors tile-blocked (default 1): tiles of
                                    4096 cells, the read-only arrays' tiles interleaved in
                                    one pool and the written arrays' in another, so a wave's
