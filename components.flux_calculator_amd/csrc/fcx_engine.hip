@@ -377,6 +377,16 @@ struct fcx_engine {
   int32_t atm_nb = 0, atm_stride = 0, atm_left = -1, atm_right = -1;
   bool own_shared = false;        // fcx_set_atmos_boundaries: the engine allocates the slots
   DevArray<double> atm_shared_own;
+  // FCX_OPT_ATMOS_INVARIANT: the boundary slots also carry the terms of the shared atmosphere
+  // cells (fcx_set_atmos_terms: K = atm_terms term columns per field behind the partial-sum
+  // columns), stored by atmos_terms_kernel after the accumulation and added in link order by the
+  // finish, so a shared cell has the bits of a one-rank engine
+  bool atm_invariant = false;
+  bool atm_terms_set = false;
+  int32_t atm_terms = 0, atm_left_pos = 0;
+  bool terms_defer = false;   // inside fcx_run_group: the terms launches of its engines are merged
+  int terms_pending = 0;      // ... the phase whose terms launch this engine still owes
+  int32_t terms_group = 0;    // engines in the terms launch of its last accumulation (0: none)
   struct fcx_comm *comm = nullptr;  // fcx_set_comm: the engine completes its boundary slots
   bool atm_done = false;            // the accumulation of the current run has been launched
   bool exchanged = false;           // ... and its boundary slots completed (comm attached)
@@ -1530,7 +1540,8 @@ static uint32_t phase_stages(int phase);
 //  - the launch itself reads the array: as qsur_in / meva_in, or an average that re-reads x[s];
 //  - it is accumulated to the atmosphere outside the launch's registers: by atmos_kernel (the
 //    accumulation is not fused, or belongs to another phase) or by the crossing-record fix-up
-//    (a launch without halo tiles on a map with crossings; pipelined chunk launches are such);
+//    (a launch without halo tiles on a map with crossings; pipelined chunk launches are such),
+//    or by the terms launch of FCX_OPT_ATMOS_INVARIANT, which reads the boundary cells' values;
 //  - a consumer in the launch needs a want bit and the kernel family does not take the
 //    unstored path (skip_family: the same rule the kernels are compiled with).
 // Per-call subroutine plans, the stages of the regrid sequence and explicit averages never skip.
@@ -1552,7 +1563,11 @@ static void plan_unread_outputs(fcx_engine *e, Plan &pl, uint32_t stages, int ph
   const bool want_ok = skip_family(e->f32, variant, ravg, tm1, merged, halo) &&
                        (!(chunked || !halo) || skip_family(e->f32, variant, ravg, tm1, merged, false));
   // the crossing-record fix-up reads the accumulated fields' arrays
-  const bool fixup_reads = fused && e->atm_crossings > 0 && (!halo || chunked);
+  // ... and so does the terms launch of FCX_OPT_ATMOS_INVARIANT (the boundary cells' terms
+  // w * x are formed from the stored values, whatever the launch's shape)
+  // (only where the engine has terms to form: boundary slots and a shared first or last cell)
+  const bool terms_read = e->atm_invariant && e->atm_terms_set && e->atm_nb > 0 && (e->atm_left >= 0 || e->atm_right >= 0);
+  const bool stored_reads = (fused && e->atm_crossings > 0 && (!halo || chunked)) || terms_read;
   std::set<const double *> read_here;
   for (int s = 0; s < P.num_types; ++s) {
     const TypeParams &tp = P.type[s];
@@ -1577,7 +1592,7 @@ static void plan_unread_outputs(fcx_engine *e, Plan &pl, uint32_t stages, int ph
     bool needs_halo = false;
     for (const auto &f : e->atm_fields) {
       if (e->buf(f.s, f.g, f.var) != b) continue;
-      if (!fused || !(f.phase & phase) || slot < 0 || pl.af.x[slot] != ptr || fixup_reads) return;
+      if (!fused || !(f.phase & phase) || slot < 0 || pl.af.x[slot] != ptr || stored_reads) return;
       needs_halo = needs_halo || e->atm_crossings > 0;
     }
     const bool consumed = slot >= 0 && ((ravg && P.ravg.out[slot]) || (fused && tm1 && pl.af.out[slot]));
@@ -1985,11 +2000,53 @@ static int constants_check(const fcx_engine *e) {
   return FCX_OK;
 }
 
+// the slot columns per boundary: the registered fields' partial sums, and with
+// FCX_OPT_ATMOS_INVARIANT the K term columns of each behind them (fcx_atmos_columns)
+static int64_t atmos_columns(const fcx_engine *e) {
+  const int64_t fields = (int64_t)e->atm_fields.size();
+  return e->atm_invariant && e->atm_terms_set ? fields * (1 + (int64_t)e->atm_terms) : fields;
+}
+
+// FCX_OPT_ATMOS_INVARIANT: what fcx_commit and fcx_plan_check refuse, on the host alone
+static int invariant_check(const fcx_engine *e) {
+  if (!e->atm_invariant || e->n_atmos < 0) return FCX_OK;
+  if (!e->atm_contiguous)
+    return fail(FCX_E_ARG, "FCX_OPT_ATMOS_INVARIANT needs a sorted atmosphere map (the exchange cells of an atmosphere "
+                           "cell next to each other, in link order); this map is unsorted");
+  if (!e->atm_terms_set) {
+    if (e->atm_nb > 0) return fail(FCX_E_ARG, "FCX_OPT_ATMOS_INVARIANT with %d boundary slots needs fcx_set_atmos_terms", e->atm_nb);
+    return FCX_OK;
+  }
+  if (e->atm_terms < 1 || e->atm_terms > kMaxAtmosTerms)
+    return fail(FCX_E_ARG, "max_terms %d outside 1..%d (the cap of fcx_set_atmos_terms)", e->atm_terms, kMaxAtmosTerms);
+  if (e->atm_left_pos < 0) return fail(FCX_E_ARG, "left_pos %d is negative", e->atm_left_pos);
+  if (!e->own_shared && e->atm_nb > 0 && e->atm_stride < atmos_columns(e))
+    return fail(FCX_E_ARG, "stride %d of the boundary slots < %lld = %zu atmosphere fields x (1 + max_terms %d)",
+                e->atm_stride, (long long)atmos_columns(e), e->atm_fields.size(), e->atm_terms);
+  if (e->n_atmos == 0) return FCX_OK;
+  const int32_t pos0 = e->atm_left >= 0 ? e->atm_left_pos : 0;
+  if (e->atm_left >= 0) {
+    const int32_t own = e->atm.row[1] - e->atm.row[0];
+    if (pos0 + own > e->atm_terms)
+      return fail(FCX_E_ARG, "left_pos %d + the %d exchange cells of the first local atmosphere cell > max_terms %d",
+                  pos0, own, e->atm_terms);
+  }
+  if (e->atm_right >= 0) {
+    const size_t c = (size_t)e->n_atmos - 1;
+    const int32_t own = e->atm.row[c + 1] - e->atm.row[c], pos = c == 0 ? pos0 : 0;
+    if (pos + own > e->atm_terms)
+      return fail(FCX_E_ARG, "left_pos %d + the %d exchange cells of the last local atmosphere cell > max_terms %d", pos,
+                  own, e->atm_terms);
+  }
+  return FCX_OK;
+}
+
 static int plan_check_all(fcx_engine *e, bool constants_only = false);
 extern "C" int fcx_plan_check(fcx_engine *e) {
   if (!e) return fail(FCX_E_ARG, "NULL engine");
   if (e->committed) return fail(FCX_E_STATE, "fcx_plan_check runs before fcx_commit");
   if (int r = validate(e)) return r;
+  if (int r = invariant_check(e)) return r;
   if (int r = received_check(e)) return r;
   if (int r = settle_output_use(e)) return r;
   decide_uniform(e);
@@ -3235,7 +3292,7 @@ static int commit_atmos_outputs(fcx_engine *e) {
 // fcx_set_atmos_boundaries: the engine's own [n_boundaries][fields] slots, zero on entry
 static int commit_shared_slots(fcx_engine *e) {
   if (!e->own_shared || e->n_atmos < 0) return FCX_OK;
-  const size_t stride = std::max<size_t>(e->atm_fields.size(), 1);
+  const size_t stride = std::max<size_t>((size_t)atmos_columns(e), 1);
   const size_t cnt = std::max<size_t>((size_t)e->atm_nb * stride, 1);
   HIP_TRY(e->atm_shared_own.alloc(cnt * sizeof(double)));
   HIP_TRY(hipMemset(e->atm_shared_own, 0, cnt * sizeof(double)));
@@ -3313,6 +3370,7 @@ extern "C" int fcx_commit(fcx_engine *e) {
   if (!e) return fail(FCX_E_ARG, "NULL engine");
   if (e->committed) return FCX_OK;
   if (int r = validate(e)) return r;
+  if (int r = invariant_check(e)) return r;
   if (int r = received_check(e)) return r;
   if (int r = settle_output_use(e)) return r;
   decide_uniform(e);
@@ -3775,7 +3833,61 @@ static AtmosArgs atmos_args(fcx_engine *e, int phase) {
     a.scol[a.nf] = (int32_t)i;
     ++a.nf;
   }
+  if (e->atm_invariant && e->atm_terms_set && e->atm_shared) {
+    a.terms_k = e->atm_terms;
+    a.term0 = (int32_t)e->atm_fields.size();
+    a.left_pos = e->atm_left_pos;
+  }
   return a;
+}
+
+// FCX_OPT_ATMOS_INVARIANT: the terms launch an engine owes after the accumulation of `phase`
+static bool terms_due(const fcx_engine *e) {
+  return e->atm_invariant && e->atm_terms_set && e->atm_shared && e->n_atmos > 0 && !e->atm_fields.empty() &&
+         (e->atm_left >= 0 || e->atm_right >= 0);
+}
+
+// the terms of n engines of one stream and precision as ONE launch (phases[k]: engine k's phase)
+static int launch_terms(fcx_engine *const *es, const int *phases, int n) {
+  AtmosArgs as[kMaxGroup];
+  bool took[kMaxGroup] = {};
+  int64_t items = 1;
+  int m = 0;
+  for (int k = 0; k < n; ++k) {
+    fcx_engine *e = es[k];
+    as[m] = atmos_args(e, phases[k]);
+    if (as[m].nf == 0) continue;
+    took[k] = true;
+    for (const auto &f : e->atm_fields)
+      if (f.phase & phases[k])
+        if (int r = stale_check(e, e->buf(f.s, f.g, f.var), "the terms of the shared atmosphere cells")) return r;
+    // a slot may have moved since commit (fcx_set_atmos_shared): the bounds once more
+    if (as[m].stride < as[m].term0 * (1 + as[m].terms_k) || as[m].left >= e->atm_nb || as[m].right >= e->atm_nb)
+      return fail(FCX_E_STATE, "boundary slots of %d x %d doubles do not hold the terms", e->atm_nb, as[m].stride);
+    const size_t c = (size_t)e->n_atmos - 1;
+    const int64_t cells = std::max(e->atm.row[1] - e->atm.row[0], e->atm.row[c + 1] - e->atm.row[c]);
+    items = std::max(items, cells * as[m].nf);
+    ++m;
+  }
+  if (m == 0) return FCX_OK;
+  const int r = launch_atmos_terms(as, m, items, es[0]->stream);
+  if (r) return fail(FCX_E_HIP, "atmos_terms launch: %s", hipGetErrorString((hipError_t)r));
+  for (int k = 0; k < n; ++k)
+    if (took[k]) es[k]->terms_group = m;
+  return FCX_OK;
+}
+
+// after an engine's accumulation is complete (fix-up and pipelined chunks included), before its
+// exchange.  Inside fcx_run_group the launch is owed (terms_pending) and the list's engines
+// share one -- unless the engine exchanges by itself (fcx_set_comm), which needs the terms now.
+static int run_terms(fcx_engine *e, int phase) {
+  e->terms_group = 0;
+  if (!terms_due(e)) return FCX_OK;
+  if (e->terms_defer && !e->comm) {
+    e->terms_pending = phase;
+    return FCX_OK;
+  }
+  return launch_terms(&e, &phase, 1);
 }
 
 static int run_atmos(fcx_engine *e, int phase) {
@@ -3870,8 +3982,10 @@ static int run_outputs(fcx_engine *e, int phase) {
   if (e->atmos_in_run && !e->atm_done_fused)
     if (int r = run_atmos(e, phase)) return r;
   e->atm_done = e->atmos_in_run || e->atm_done_fused;
-  if (e->atm_done)
+  if (e->atm_done) {
+    if (int r = run_terms(e, phase)) return r;
     if (int r = comm_exchange(e)) return r;
+  }
   return run_remaps(e, phase);
 }
 
@@ -4400,6 +4514,7 @@ static int run_phase(fcx_engine *e, int phase, int32_t t) {
   if (e->timing) HIP_TRY(hipEventRecord(e->ev0, e->stream));
   e->atm_done_fused = false;
   e->atm_done = e->exchanged = false;
+  e->terms_group = 0;
   e->rec_plan = nullptr;
   e->group_members = 0;
   fields_taken(e);
@@ -4503,6 +4618,21 @@ extern "C" int fcx_run_group(fcx_engine *const *es, int n, int phase, int32_t t)
     if (int r = run_gathers(m.e, phase)) return r;
   if (!mem.empty())
     if (int r = launch_group(mem.data(), (int)mem.size())) return r;
+  // FCX_OPT_ATMOS_INVARIANT: the list's terms launches are owed during the tails and queued as
+  // one launch per stream and precision behind them (each dependent launch is ~5 us of the step)
+  struct TermsDefer {
+    fcx_engine *const *es;
+    int n;
+    TermsDefer(fcx_engine *const *es_, int n_) : es(es_), n(n_) {
+      for (int i = 0; i < n; ++i) es[i]->terms_defer = true, es[i]->terms_pending = 0;
+    }
+    ~TermsDefer() {  // a launch still owed here was never queued (an error ended the call): that
+      for (int i = 0; i < n; ++i) {  // engine's slots hold no terms, so it has no accumulation to exchange
+        if (es[i]->terms_pending) es[i]->atm_done = false;
+        es[i]->terms_defer = false, es[i]->terms_pending = 0;
+      }
+    }
+  } defer(es, n);
   for (int i = 0; i < n; ++i) {
     fcx_engine *e = es[i];
     if (member_of[(size_t)i] < 0) {
@@ -4513,6 +4643,19 @@ extern "C" int fcx_run_group(fcx_engine *const *es, int n, int phase, int32_t t)
     e->atm_done_fused = true;
     if (int r = run_tail(e, phase)) return r;
     if (int r = queue_checks(e, phase)) return r;
+  }
+  for (int i = 0; i < n; ++i) {
+    if (!es[i]->terms_pending) continue;
+    fcx_engine *ge[kMaxGroup];
+    int gp[kMaxGroup], ng = 0;
+    for (int j = i; j < n && ng < kMaxGroup; ++j)
+      if (es[j]->terms_pending && es[j]->stream == es[i]->stream && es[j]->f32 == es[i]->f32 &&
+          std::find(ge, ge + ng, es[j]) == ge + ng) {
+        ge[ng] = es[j];
+        gp[ng++] = es[j]->terms_pending;
+      }
+    for (int k = 0; k < ng; ++k) ge[k]->terms_pending = 0;
+    if (int r = launch_terms(ge, gp, ng)) return r;
   }
   // FCX_OPT_CHECK_FINITE: every engine's work, its collectives included, is queued by now; the
   // verdicts are read in list order and the first offender is the call's error
@@ -4533,6 +4676,7 @@ static void group_members(const GroupLaunchMember *mem, int nm, GroupMember *gm)
     fcx_engine *e = m.e;
     e->atm_done_fused = false;
     e->atm_done = e->exchanged = false;
+    e->terms_group = 0;
     e->rec_plan = nullptr;
     e->rec_written = false;
     fields_taken(e);
@@ -4671,6 +4815,7 @@ static int step_pipelined(fcx_engine *e, int phase, int32_t t, Plan *pl) {
   if (e->timing) HIP_TRY(hipEventRecord(e->ev0, e->s_in));
   e->atm_done_fused = false;
   e->atm_done = e->exchanged = false;
+  e->terms_group = 0;
   e->rec_plan = pl;
   for (int k = 0; k < K; ++k) {
     const int64_t lo = k * per, hi = std::min(n, lo + per);
@@ -5099,6 +5244,12 @@ extern "C" int fcx_set_option(fcx_engine *e, int option, int64_t value) {
       if (value < 0 || value > 1) return fail(FCX_E_ARG, "cr_math: 0 the device library's exp and log, 1 correctly rounded");
       e->cr_math = value != 0;
       return FCX_OK;
+    case FCX_OPT_ATMOS_INVARIANT:
+      if (e->committed) return fail(FCX_E_STATE, "atmos_invariant is applied at fcx_commit");
+      if (value < 0 || value > 1)
+        return fail(FCX_E_ARG, "atmos_invariant: 0 partial sums in the boundary slots, 1 the terms in link order");
+      e->atm_invariant = value != 0;
+      return FCX_OK;
     case FCX_OPT_CHECK_FINITE:
       if (e->committed) return fail(FCX_E_STATE, "check_finite is applied at fcx_commit");
       if (value < 0 || value > 3) return fail(FCX_E_ARG, "check_finite: bit 0 the outputs, bit 1 the inputs (0..3)");
@@ -5201,6 +5352,10 @@ extern "C" int fcx_set_atmos_shared(fcx_engine *e, double *shared, int32_t nb, i
     return fail(FCX_E_ARG, "the one atmosphere cell is shared on both sides: it needs one boundary slot for all "
                            "its ranks (left == right), not %d and %d", left, right);
   if (e->own_shared) return fail(FCX_E_STATE, "boundary slots already owned by the engine (fcx_set_atmos_boundaries)");
+  // (before fcx_commit the option and K may still change: fcx_commit checks the stride then)
+  if (e->committed && nb > 0 && e->atm_invariant && e->atm_terms_set && stride < atmos_columns(e))
+    return fail(FCX_E_ARG, "stride %d of the boundary slots < %lld = %zu atmosphere fields x (1 + max_terms %d)", stride,
+                (long long)atmos_columns(e), e->atm_fields.size(), e->atm_terms);
   e->atm_shared = shared;
   e->atm_nb = nb;
   e->atm_stride = stride;
@@ -5230,6 +5385,7 @@ extern "C" int fcx_run_atmos(fcx_engine *e, int phase) {
   if (!e->atm_done) {  // not done inside the last fcx_run (FCX_OPT_ATMOS_IN_RUN = 0, not fused)
     if (int r = run_atmos(e, phase)) return r;
     e->atm_done = true;
+    if (int r = run_terms(e, phase)) return r;
   }
   return comm_exchange(e);  // no-op without a communicator, or when fcx_run already exchanged
 }
@@ -5250,6 +5406,35 @@ extern "C" int fcx_f32_math(const fcx_engine *e, int32_t *on) {
 extern "C" int fcx_cr_math(const fcx_engine *e, int32_t *on) {
   if (!e || !on) return fail(FCX_E_ARG, "NULL argument");
   *on = e->committed && e->cr() ? 1 : 0;
+  return FCX_OK;
+}
+
+extern "C" int fcx_atmos_invariant(const fcx_engine *e, int32_t *on) {
+  if (!e || !on) return fail(FCX_E_ARG, "NULL argument");
+  *on = e->atm_invariant ? 1 : 0;
+  return FCX_OK;
+}
+
+extern "C" int fcx_last_terms_group(const fcx_engine *e, int32_t *engines) {
+  if (!e || !engines) return fail(FCX_E_ARG, "NULL argument");
+  *engines = e->terms_group;
+  return FCX_OK;
+}
+
+extern "C" int fcx_set_atmos_terms(fcx_engine *e, int32_t max_terms, int32_t left_pos) {
+  if (!e) return fail(FCX_E_ARG, "NULL engine");
+  if (e->committed) return fail(FCX_E_STATE, "engine already committed");
+  // (what the two numbers must satisfy depends on the map, the slots and the option, which may
+  // all follow: fcx_plan_check and fcx_commit check them, by name)
+  e->atm_terms = max_terms;
+  e->atm_left_pos = left_pos;
+  e->atm_terms_set = true;
+  return FCX_OK;
+}
+
+extern "C" int fcx_atmos_columns(const fcx_engine *e, int32_t *columns) {
+  if (!e || !columns) return fail(FCX_E_ARG, "NULL argument");
+  *columns = (int32_t)atmos_columns(e);
   return FCX_OK;
 }
 

@@ -297,8 +297,25 @@ struct AtmosArgs {
   int32_t scol[kMaxAtmosFields];  // column of field f in the shared boundary slots: the
                                   // field's registration index (fcx_add_atmos_field order),
                                   // the same for every phase and for the fused kernel
+  // FCX_OPT_ATMOS_INVARIANT (0 everywhere with the option off): terms_k = K > 0 says the slots
+  // carry, behind the term0 partial-sum columns (term0: the registered fields), K term columns
+  // per registered field -- column term0 + scol[f] * K + p holds the term at link position p --
+  // and left_pos is the position of this rank's first exchange cell within its first
+  // atmosphere cell (fcx_set_atmos_terms)
+  int32_t terms_k;
+  int32_t term0;
+  int32_t left_pos;
 };
 int launch_atmos(const AtmosArgs &a, void *stream);
+// FCX_OPT_ATMOS_INVARIANT: the terms w[x] * field[x] of the first and last local atmosphere
+// cells of n engines (same precision, one stream; n <= kMaxGroup) into the term columns of their
+// boundary slots, ONE launch (fcx_atmos_terms.hip).  max_items: the largest (cells x fields) of
+// any boundary cell, which sizes the grid.  Engines without a slot or with terms_k == 0 are
+// passed over.
+// The largest K fcx_set_atmos_terms takes: the ordered finish adds a slot's K terms in one
+// thread, and a region row is fields * (1 + K) doubles
+constexpr int32_t kMaxAtmosTerms = 4096;
+int launch_atmos_terms(const AtmosArgs *as, int n, int64_t max_items, void *stream);
 // atmos_finish of several engines (same precision, one stream) in one launch
 struct FinishGroup;
 int launch_atmos_finish_group(const AtmosArgs *as, const int32_t *n_boundaries, int n, void *stream);

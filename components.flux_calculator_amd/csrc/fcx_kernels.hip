@@ -1792,12 +1792,35 @@ __global__ __launch_bounds__(256) void pack_records_kernel(const AtmosArgs a, in
   }
 }
 
+// FCX_OPT_ATMOS_INVARIANT: the ordered finish of one engine (a.terms_k = K > 0).  After the
+// all-reduce the term columns of a boundary slot hold the terms w[x] * field[x] of ALL the ranks'
+// cells of the shared atmosphere cell, each at its link position (fcx_atmos_terms.hip).  Thread
+// t = (boundary side, field) adds the K positions in order from +0.0 -- the sequential sum of a
+// one-rank engine -- and stores it rounded once to R.  Positions past the cell's last link hold
+// +0.0, and a -0.0 term arrives as +0.0 through the sum all-reduce (-0.0 + 0.0 = +0.0): adding
+// either changes nothing, because the sum starts from +0.0 and so is never -0.0 (x + 0.0 = x for
+// every x but -0.0).  The partial-sum columns scol[f] the accumulation kernels wrote are ignored.
+template <class R>
+__device__ __forceinline__ void finish_ordered(const AtmosArgs &a, int t) {
+  if (t >= 2 * a.nf) return;
+  const int side = t >= a.nf, f = side ? t - a.nf : t;
+  const int32_t slot = side ? a.right : a.left;
+  if (slot < 0) return;
+  const int32_t K = a.terms_k;
+  const double *term = a.shared + (int64_t)slot * a.stride + a.term0 + (int64_t)a.scol[f] * K;
+  double acc = 0.0;
+  for (int32_t p = 0; p < K; ++p) acc = acc + term[p];
+  reinterpret_cast<R *>(a.out[f])[side ? atm_at(a.n_atmos - 1, a.out_stride, a.out_tpad) : 0] = (R)acc;
+}
+
 // after the all-reduce: completed boundary sums back into the outputs, then every slot of
 // this engine's region is zeroed for the next step (one block)
 template <class R>
 __global__ void atmos_finish_kernel(const AtmosArgs a, int32_t n_boundaries) {
   const int t = threadIdx.x;
-  if (t < a.nf) {
+  if (a.terms_k > 0) {
+    finish_ordered<R>(a, t);
+  } else if (t < a.nf) {
     R *out = reinterpret_cast<R *>(a.out[t]);
     if (a.left >= 0) out[0] = (R)a.shared[(int64_t)a.left * a.stride + a.scol[t]];
     if (a.right >= 0) out[atm_at(a.n_atmos - 1, a.out_stride, a.out_tpad)] = (R)a.shared[(int64_t)a.right * a.stride + a.scol[t]];
@@ -1813,7 +1836,9 @@ __global__ void atmos_finish_group_kernel(const FinishGroup g) {
   const AtmosArgs &a = g.a[blockIdx.x];
   const int32_t n_boundaries = g.nb[blockIdx.x];
   const int t = threadIdx.x;
-  if (t < a.nf) {
+  if (a.terms_k > 0) {
+    finish_ordered<R>(a, t);
+  } else if (t < a.nf) {
     R *out = reinterpret_cast<R *>(a.out[t]);
     if (a.left >= 0) out[0] = (R)a.shared[(int64_t)a.left * a.stride + a.scol[t]];
     if (a.right >= 0) out[atm_at(a.n_atmos - 1, a.out_stride, a.out_tpad)] = (R)a.shared[(int64_t)a.right * a.stride + a.scol[t]];

@@ -28,7 +28,8 @@ MODULE fcx_c_api
                                FCX_OPT_ATMOS_HALO = 17, FCX_OPT_DEFERRED_SCATTER = 18, &
                                FCX_OPT_LIB_SPANS = 19, FCX_OPT_ATM_RECORDS = 21, &
                                FCX_OPT_F32_MATH = 22, FCX_OPT_CHECK_FINITE = 23, &
-                               FCX_OPT_CR_MATH = 24, FCX_OPT_SUM_BASELINE = 25
+                               FCX_OPT_CR_MATH = 24, FCX_OPT_SUM_BASELINE = 25, &
+                               FCX_OPT_ATMOS_INVARIANT = 26
   ! the non-finite guard (FCX_OPT_CHECK_FINITE) found a NaN or an Inf
   INTEGER(c_int), PARAMETER :: FCX_E_NONFINITE = 7
   ! struct fcx_field_range: min / max over the cells that are not NaN, the NaN and Inf counts, the
@@ -297,6 +298,35 @@ MODULE fcx_c_api
       TYPE(c_ptr), VALUE :: engine
       INTEGER(c_int32_t), VALUE :: n_boundaries, left, right
       INTEGER(c_int) :: fcx_set_atmos_boundaries
+    END FUNCTION
+    ! FCX_OPT_ATMOS_INVARIANT: max_terms term columns per field in the boundary slots (the same
+    ! on every rank) and the position of this rank's first cell in its first atmosphere cell
+    FUNCTION fcx_set_atmos_terms(engine, max_terms, left_pos) BIND(C, name='fcx_set_atmos_terms')
+      IMPORT :: c_int, c_int32_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int32_t), VALUE :: max_terms, left_pos
+      INTEGER(c_int) :: fcx_set_atmos_terms
+    END FUNCTION
+    ! doubles per boundary slot: the fields, times 1 + max_terms with FCX_OPT_ATMOS_INVARIANT
+    FUNCTION fcx_atmos_columns(engine, columns) BIND(C, name='fcx_atmos_columns')
+      IMPORT :: c_int, c_int32_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int32_t), INTENT(OUT) :: columns
+      INTEGER(c_int) :: fcx_atmos_columns
+    END FUNCTION
+    ! engines in the terms launch of this engine's last accumulation (0: none)
+    FUNCTION fcx_last_terms_group(engine, engines) BIND(C, name='fcx_last_terms_group')
+      IMPORT :: c_int, c_int32_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int32_t), INTENT(OUT) :: engines
+      INTEGER(c_int) :: fcx_last_terms_group
+    END FUNCTION
+    ! 1 = FCX_OPT_ATMOS_INVARIANT is on
+    FUNCTION fcx_atmos_invariant(engine, on) BIND(C, name='fcx_atmos_invariant')
+      IMPORT :: c_int, c_int32_t, c_ptr
+      TYPE(c_ptr), VALUE :: engine
+      INTEGER(c_int32_t), INTENT(OUT) :: on
+      INTEGER(c_int) :: fcx_atmos_invariant
     END FUNCTION
     FUNCTION fcx_atmos_finish(engine) BIND(C, name='fcx_atmos_finish')
       IMPORT :: c_int, c_ptr

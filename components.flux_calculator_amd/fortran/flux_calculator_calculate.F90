@@ -14,6 +14,8 @@
 !                           a sender (optional: the field is then never transferred)
 !   fcx_define_receive_map /  for each input the host receives on its model's grid (optional: the
 !   fcx_declare_received    engine expands it to the exchange grid on the device)
+!   fcx_define_atmos_terms  once (optional: atmosphere sums that are the same bits for any number
+!                           of ranks, FCX_OPT_ATMOS_INVARIANT)
 !   fcx_select_outputs      once, with the host's output_field (optional: the computed fluxes no
 !                           output_field entry sends are neither downloaded nor, where nothing
 !                           else reads them, stored)
@@ -53,7 +55,7 @@ MODULE flux_calculator_calculate
     PUBLIC fcx_declare_constant
     PUBLIC fcx_select_outputs
     PUBLIC fcx_define_receive_map, fcx_declare_received
-    PUBLIC fcx_check_finite, fcx_field_range_of
+    PUBLIC fcx_check_finite, fcx_field_range_of, fcx_define_atmos_terms, fcx_engine_handle
     PUBLIC fcx_declare_areas, fcx_field_integral_of
 
     TYPE(c_ptr), SAVE :: engine = c_null_ptr
@@ -423,6 +425,30 @@ CONTAINS
         INTEGER, INTENT(IN) :: what
         CALL check(fcx_set_option(engine, FCX_OPT_CHECK_FINITE, INT(what, c_int64_t)), 'fcx_check_finite')
     END SUBROUTINE fcx_check_finite
+
+    ! Atmosphere sums that do not depend on the number of ranks (FCX_OPT_ATMOS_INVARIANT), before
+    ! fcx_commit_engine.  max_terms: the largest number of exchange cells of any atmosphere cell
+    ! shared between ranks, the same on every rank (an MPI_Allreduce(MAX) of the ranks' own
+    ! counts); left_pos: how many exchange cells of this rank's first atmosphere cell lie on lower
+    ! ranks (a prefix over the ranks holding that cell; 0 when the cell begins here).
+    ! INTEGRATION.md section 3 shows both.  The boundary slots the host hands over with
+    ! fcx_set_atmos_shared then need fcx_atmos_columns doubles per boundary.
+    SUBROUTINE fcx_define_atmos_terms(max_terms, left_pos)
+        INTEGER, INTENT(IN) :: max_terms, left_pos
+        IF (.NOT. c_associated(engine)) CALL contract_error('fcx_define_atmos_terms', 'no flux engine attached')
+        CALL check(fcx_set_option(engine, FCX_OPT_ATMOS_INVARIANT, 1_c_int64_t), 'fcx_define_atmos_terms')
+        CALL check(fcx_set_atmos_terms(engine, INT(max_terms, c_int32_t), INT(left_pos, c_int32_t)), &
+                   'fcx_set_atmos_terms')
+    END SUBROUTINE fcx_define_atmos_terms
+
+    ! The attached engine, for what the module has no routine of its own for: a host that adds the
+    ! exchange -> atmosphere accumulation calls fcx_set_atmos_map, fcx_add_atmos_field,
+    ! fcx_set_atmos_shared and fcx_atmos_finish of fcx_c_api on it (INTEGRATION.md section 5).
+    ! c_null_ptr when no engine is attached.
+    FUNCTION fcx_engine_handle() RESULT(h)
+        TYPE(c_ptr) :: h
+        h = engine
+    END FUNCTION fcx_engine_handle
 
     ! MINVAL / MAXVAL of local_field(surface_type, which_grid)%var(my_idx) as the engine holds
     ! it on the device, for a host's own DEBUG lines (flux_calculator.F90:879-881, 921-924,

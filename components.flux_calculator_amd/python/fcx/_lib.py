@@ -25,6 +25,7 @@ FCX_OPT_F32_MATH = 22  # an fp32 engine's fluxes computed in double (fcx_set_opt
 FCX_OPT_CHECK_FINITE = 23  # the non-finite guard: bit 0 the phase's outputs, bit 1 its inputs
 FCX_OPT_CR_MATH = 24  # an fp64 engine's exp and Exner power correctly rounded (fcx_set_option)
 FCX_OPT_SUM_BASELINE = 25  # measurement: the integral launches without the lanes' register windows
+FCX_OPT_ATMOS_INVARIANT = 26  # shared atmosphere cells summed term by term: bits of a one-rank engine
 FCX_E_NONFINITE = 7
 FCX_SUM_LIMBS = 68
 FCX_COMM_ID_BYTES = 128
@@ -122,6 +123,10 @@ SIGNATURES = [
     ("fcx_atm_records", _I, [_P, _c.POINTER(_I32)]),
     ("fcx_f32_math", _I, [_P, _c.POINTER(_I32)]),
     ("fcx_cr_math", _I, [_P, _c.POINTER(_I32)]),
+    ("fcx_atmos_invariant", _I, [_P, _c.POINTER(_I32)]),
+    ("fcx_set_atmos_terms", _I, [_P, _I32, _I32]),
+    ("fcx_atmos_columns", _I, [_P, _c.POINTER(_I32)]),
+    ("fcx_last_terms_group", _I, [_P, _c.POINTER(_I32)]),
     ("fcx_fused_accumulation", _I, [_P, _I, _c.POINTER(_I32)]),
     ("fcx_step_async", _I, [_P, _I, _I32]),
     ("fcx_upload_field", _I, [_P, _I, _I, _I]),

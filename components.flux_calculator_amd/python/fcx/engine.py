@@ -132,6 +132,10 @@ class Engine:
                        (fcx_set_atmos_boundaries) from local.n_boundaries/left/right
              comm    : optional fcx.comm.Comm: the engine completes its boundary slots
                        itself after every accumulation (fcx_set_comm)
+             invariant : optional True: FCX_OPT_ATMOS_INVARIANT with local.max_terms and
+                       local.left_pos (fcx_set_atmos_terms): shared atmosphere cells have the
+                       bits of a one-rank engine; a `shared` buffer then needs a stride of
+                       fields x (1 + max_terms) doubles (Engine.atmos_columns)
         remaps: exchange -> model remaps, each {"n_dst", "src", "dst", "w" (0-based links),
                  "fields": [(phase, surface_type, grid, name, out_array[n_dst])]}
         options: {name: value} for fcx_set_option.
@@ -236,6 +240,11 @@ class Engine:
                     self._keep.append(out)
                     _lib.check(self.lib.fcx_add_atmos_field(h, phase, s, g, IDX[name],
                                                             ctypes.c_void_p(data_ptr(out)), flags))
+                if atmos.get("invariant"):
+                    # sums that do not depend on the number of ranks: the boundary slots carry
+                    # the shared cells' terms (max_terms term columns per field)
+                    _lib.check(self.lib.fcx_set_option(h, _lib.FCX_OPT_ATMOS_INVARIANT, 1))
+                    _lib.check(self.lib.fcx_set_atmos_terms(h, int(la.max_terms), int(la.left_pos)))
                 if atmos.get("shared") is not None:
                     buf, stride = atmos["shared"]
                     self._keep.append(buf)
@@ -353,7 +362,8 @@ class Engine:
                "timing": 10, "tiled_layout": 11, "remap_pack": 13, "host_staging": 15, "host_threads": 16,
                "atmos_halo": 17, "deferred_scatter": 18, "lib_spans": 19, "atm_records": 21,
                "f32_math": _lib.FCX_OPT_F32_MATH, "check_finite": _lib.FCX_OPT_CHECK_FINITE,
-               "cr_math": _lib.FCX_OPT_CR_MATH, "sum_baseline": _lib.FCX_OPT_SUM_BASELINE}
+               "cr_math": _lib.FCX_OPT_CR_MATH, "sum_baseline": _lib.FCX_OPT_SUM_BASELINE,
+               "atmos_invariant": _lib.FCX_OPT_ATMOS_INVARIANT}
 
     def run_atmos(self, phase=PHASE_ALL):
         _lib.check(self.lib.fcx_run_atmos(self.h, phase))
@@ -479,6 +489,26 @@ class Engine:
         on = ctypes.c_int32()
         _lib.check(self.lib.fcx_cr_math(self.h, ctypes.byref(on)))
         return bool(on.value)
+
+    def atmos_invariant(self):
+        """True when FCX_OPT_ATMOS_INVARIANT is on (fcx_atmos_invariant)."""
+        on = ctypes.c_int32()
+        _lib.check(self.lib.fcx_atmos_invariant(self.h, ctypes.byref(on)))
+        return bool(on.value)
+
+    def last_terms_group(self):
+        """Engines whose terms shared one launch with this engine's after its last accumulation
+        (fcx_last_terms_group; 0: no terms launch)."""
+        m = ctypes.c_int32()
+        _lib.check(self.lib.fcx_last_terms_group(self.h, ctypes.byref(m)))
+        return m.value
+
+    def atmos_columns(self):
+        """Doubles per boundary slot (fcx_atmos_columns): the accumulated fields, times
+        1 + max_terms with FCX_OPT_ATMOS_INVARIANT."""
+        n = ctypes.c_int32()
+        _lib.check(self.lib.fcx_atmos_columns(self.h, ctypes.byref(n)))
+        return n.value
 
     def fused_accumulation(self, phase=PHASE_ALL):
         """True when the phase's exchange -> atmosphere accumulation rides inside the flux launch,

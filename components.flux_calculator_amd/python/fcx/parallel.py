@@ -92,6 +92,56 @@ class LocalAtmos:
     left: int  # boundary slot of the first local atmosphere cell, -1 = not shared
     right: int  # boundary slot of the last one, -1 = not shared
     n_boundaries: int
+    # FCX_OPT_ATMOS_INVARIANT (fcx_set_atmos_terms, boundary_terms): how many exchange cells of
+    # the first local atmosphere cell lie on lower ranks, and the run's K (0: not worked out)
+    left_pos: int = 0
+    max_terms: int = 0
+
+
+def _run_end(index_at, lo, hi, a):
+    """First x in [lo, hi) with index_at(x) != a, given index_at(lo) == a and a non-decreasing
+    index (hi if there is none)."""
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        if int(index_at(mid)) == a:
+            lo = mid
+        else:
+            hi = mid
+    return hi
+
+
+def boundary_terms(ranges, index_at):
+    """(max_terms, [left_pos of every rank]) for fcx_set_atmos_terms (FCX_OPT_ATMOS_INVARIANT).
+
+    ranges, index_at: as boundary_slots.  left_pos of a rank is the number of exchange cells of
+    its first atmosphere cell that lie on lower ranks (0 for a rank without cells, or whose first
+    cell begins on it); max_terms is the largest number of exchange cells of any atmosphere cell
+    held by two or more ranks, and 1 where no cell is shared (the term columns need a width)."""
+    left_pos = [0] * len(ranges)
+    k_max, prev_a1, carried = 0, None, 0  # carried: cells of atmosphere cell prev_a1 so far
+    for k, (off, size) in enumerate(ranges):
+        if size == 0:
+            continue
+        end = off + size
+        a0, a1 = int(index_at(off)), int(index_at(end - 1))
+        first = _run_end(index_at, off, end, a0) - off  # this rank's cells of its first cell
+        pos = carried if prev_a1 == a0 else 0
+        left_pos[k] = pos
+        if pos:
+            k_max = max(k_max, pos + first)
+        if a1 == a0:
+            carried = pos + first
+        else:
+            lo, hi = off, end - 1  # the last cell's first exchange cell on this rank
+            while hi - lo > 1:
+                mid = (lo + hi) // 2
+                if int(index_at(mid)) == a1:
+                    hi = mid
+                else:
+                    lo = mid
+            carried = end - hi
+        prev_a1 = a1
+    return max(k_max, 1), left_pos
 
 
 def boundary_slots(ranges, index_at):
@@ -129,11 +179,17 @@ def local_atmos(amap: AtmosMap, rank, nranks, offset=None, size=None, right_slot
     if ranges is not None:
         offset, size = ranges[rank]
     gi = amap.atmos_index[offset: offset + size]
-    if size == 0:
-        return LocalAtmos(offset, 0, 0, 0, np.zeros(0, np.int32), np.zeros(0), -1, -1, max(nranks - 1, 0))
+    if size == 0:  # (a rank without cells still takes part in the exchange: it needs the run's K)
+        k = boundary_terms(ranges, lambda x: amap.atmos_index[x])[0] if ranges is not None else 0
+        return LocalAtmos(offset, 0, 0, 0, np.zeros(0, np.int32), np.zeros(0), -1, -1, max(nranks - 1, 0), 0, k)
     a0, a1 = int(gi[0]), int(gi[-1])
+    # left_pos from the map itself; max_terms needs every rank's range (0 without them)
+    left_pos = int(offset - np.searchsorted(amap.atmos_index, a0, side="left"))
+    max_terms = 0
     if ranges is not None:
         left, right = boundary_slots(ranges, lambda x: amap.atmos_index[x])[rank]
+        max_terms, pos = boundary_terms(ranges, lambda x: amap.atmos_index[x])
+        left_pos = pos[rank]
     else:
         left = rank - 1 if (offset > 0 and amap.atmos_index[offset - 1] == a0) else -1
         end = offset + size
@@ -144,7 +200,7 @@ def local_atmos(amap: AtmosMap, rank, nranks, offset=None, size=None, right_slot
                              "with both neighbours: pass every rank's ranges to give it one slot")
     return LocalAtmos(offset, size, a0, a1 - a0 + 1, np.ascontiguousarray(gi - a0, dtype=np.int32),
                       np.ascontiguousarray(amap.weight[offset: offset + size]), left, right,
-                      max(nranks - 1, 0))
+                      max(nranks - 1, 0), left_pos, max_terms)
 
 
 def owned_atmos_mask(la: LocalAtmos):
@@ -221,17 +277,22 @@ class PeriodicAtmosMap:
         right_slot = rank if right_slot is None else right_slot
         x = np.arange(offset, offset + size, dtype=np.int64)
         gi = self.index(x)
-        if size == 0:
-            return LocalAtmos(offset, 0, 0, 0, np.zeros(0, np.int32), np.zeros(0), -1, -1, max(nranks - 1, 0))
+        if size == 0:  # (a rank without cells still takes part in the exchange: it needs the run's K)
+            k = boundary_terms(ranges, lambda c: int(self.index(c)))[0] if ranges is not None else 0
+            return LocalAtmos(offset, 0, 0, 0, np.zeros(0, np.int32), np.zeros(0), -1, -1, max(nranks - 1, 0), 0, k)
         a0, a1 = int(gi[0]), int(gi[-1])
+        left_pos, max_terms = 0, 0
         if ranges is not None:
             left, right = boundary_slots(ranges, lambda c: int(self.index(c)))[rank]
+            max_terms, pos = boundary_terms(ranges, lambda c: int(self.index(c)))
+            left_pos = pos[rank]
         else:
             left = rank - 1 if (offset > 0 and int(self.index(offset - 1)) == a0) else -1
             end = offset + size
             right = right_slot if (end < n_global and int(self.index(end)) == a1) else -1
         return LocalAtmos(offset, size, a0, a1 - a0 + 1, np.ascontiguousarray(gi - a0, dtype=np.int32),
-                          np.ascontiguousarray(self.weight(x, n_global)), left, right, max(nranks - 1, 0))
+                          np.ascontiguousarray(self.weight(x, n_global)), left, right, max(nranks - 1, 0),
+                          left_pos, max_terms)
 
     def global_map(self, n_global):
         x = np.arange(n_global, dtype=np.int64)
@@ -279,20 +340,27 @@ class BlockedRandomAtmosMap:
     def local(self, offset, size, rank, nranks, n_global, right_slot=None, ranges=None):
         """right_slot, ranges: as PeriodicAtmosMap.local."""
         right_slot = rank if right_slot is None else right_slot
-        if size == 0:
-            return LocalAtmos(offset, 0, 0, 0, np.zeros(0, np.int32), np.zeros(0), -1, -1, max(nranks - 1, 0))
+        if size == 0:  # (as PeriodicAtmosMap.local: an empty rank carries the run's K)
+            k = 0
+            if ranges is not None:
+                k = boundary_terms(ranges, lambda c: int(self._cells(c, c + 1, n_global)[0][0]))[0]
+            return LocalAtmos(offset, 0, 0, 0, np.zeros(0, np.int32), np.zeros(0), -1, -1, max(nranks - 1, 0), 0, k)
         lo, hi = max(offset - 1, 0), min(offset + size + 1, n_global)  # one neighbour cell each side
         gi, w = self._cells(lo, hi, n_global)
         mine = slice(offset - lo, offset - lo + size)
         g, wm = gi[mine], w[mine]
         a0, a1 = int(g[0]), int(g[-1])
+        left_pos, max_terms = 0, 0
         if ranges is not None:
-            left, right = boundary_slots(ranges, lambda c: int(self._cells(c, c + 1, n_global)[0][0]))[rank]
+            at = lambda c: int(self._cells(c, c + 1, n_global)[0][0])  # noqa: E731
+            left, right = boundary_slots(ranges, at)[rank]
+            max_terms, pos = boundary_terms(ranges, at)
+            left_pos = pos[rank]
         else:
             left = rank - 1 if (offset > 0 and int(gi[0]) == a0) else -1
             right = right_slot if (offset + size < n_global and int(gi[-1]) == a1) else -1
         return LocalAtmos(offset, size, a0, a1 - a0 + 1, np.ascontiguousarray(g - a0, dtype=np.int32),
-                          np.ascontiguousarray(wm), left, right, max(nranks - 1, 0))
+                          np.ascontiguousarray(wm), left, right, max(nranks - 1, 0), left_pos, max_terms)
 
     def global_map(self, n_global):
         idx, w = self._cells(0, n_global, n_global)

@@ -449,7 +449,7 @@ class FluxCalculatorSetup:
         return out
 
     def engine(self, corrections=None, regrid=None, select_outputs=False, receive_maps=None, check_finite=0,
-               areas=None, **kw):
+               areas=None, rank_invariant=False, **kw):
         """An fcx.Engine over the set-up's local_field (methods, averages, put_to).
         select_outputs: the unsent outputs are declared FCX_OUT_UNREAD (fcx_set_output_use), so
         they are neither downloaded nor, where nothing else reads them, stored.
@@ -461,9 +461,17 @@ class FluxCalculatorSetup:
         inputs too; a step that finds a NaN or an Inf raises fcx._lib.NonFiniteError.
         areas: {which_grid (1..3, or "atmos"): cell areas} for the flux budgets (Engine.set_areas,
         set_atmos_areas; fcx.driver's budgets lines).  An entry is this rank's array, or the dict
-        fcx.io.read_scrip_grid returns, whose global "area" is cut to the rank's window."""
+        fcx.io.read_scrip_grid returns, whose global "area" is cut to the rank's window.
+        rank_invariant: FCX_OPT_ATMOS_INVARIANT for the atmos= accumulation passed along (its
+        LocalAtmos carries max_terms and left_pos): the atmosphere fields are the same bits for
+        any number of ranks."""
         from . import _lib
         from .engine import Engine
+
+        if rank_invariant:
+            if kw.get("atmos") is None:
+                raise ValueError("rank_invariant=True needs the atmos= accumulation it applies to")
+            kw["atmos"] = dict(kw["atmos"], invariant=True)
 
         if check_finite:
             kw["options"] = dict(kw.pop("options", None) or {}, check_finite=int(check_finite))

@@ -8,7 +8,7 @@ mkdir -p "$OUT/obj"
 FLAGS="-DFCX_AB_BUILD --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -Wall -Wno-unused-function -I$HERE/csrc -I$HERE/../include"
 # the Makefile's translation units, side by side; each job is waited for by its pid, so a
 # failed compile fails the script
-UNITS="fcx_kernels fcx_kernels_wide fcx_kernels_cr fcx_integrals fcx_engine"
+UNITS="fcx_kernels fcx_kernels_wide fcx_kernels_cr fcx_integrals fcx_atmos_terms fcx_engine"
 OBJS=""
 PIDS=""
 for u in $UNITS; do

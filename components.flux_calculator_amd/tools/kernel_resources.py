@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """VGPRs / scratch / occupancy of every kernel in fcx_kernels.hip, fcx_kernels_wide.hip,
-fcx_kernels_cr.hip and fcx_integrals.hip
+fcx_kernels_cr.hip, fcx_integrals.hip and fcx_atmos_terms.hip
 (compiler remarks; a translation unit the checkout does not have is left out).
 
   python tools/kernel_resources.py [filter]
@@ -13,7 +13,8 @@ import tempfile
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 rows = []
-for unit in ("fcx_kernels.hip", "fcx_kernels_wide.hip", "fcx_kernels_cr.hip", "fcx_integrals.hip"):
+for unit in ("fcx_kernels.hip", "fcx_kernels_wide.hip", "fcx_kernels_cr.hip", "fcx_integrals.hip",
+             "fcx_atmos_terms.hip"):
     src = os.path.join(HERE, "..", "csrc", unit)
     if not os.path.exists(src):
         continue

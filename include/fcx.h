@@ -527,6 +527,38 @@ int fcx_set_atmos_shared(fcx_engine *e, double *shared, int32_t n_boundaries, in
  * itself (device memory, zeroed; stride = number of fcx_add_atmos_field fields).  Before
  * fcx_commit. */
 int fcx_set_atmos_boundaries(fcx_engine *e, int32_t n_boundaries, int32_t left, int32_t right);
+/* FCX_OPT_ATMOS_INVARIANT: the term columns of the boundary slots.  Before fcx_commit.
+ * max_terms (K): the largest number of exchange cells of any atmosphere cell shared between
+ * ranks, the SAME number on every rank of the run (1 .. 4096).  left_pos: how many exchange
+ * cells of this rank's FIRST local atmosphere cell lie on lower ranks (0 when left < 0).  The
+ * last local atmosphere cell needs no number: where it is another cell than the first it
+ * begins on this rank, at position 0; where it is the same cell (n_atmos == 1) its position is
+ * left_pos.  (fcx.parallel.boundary_terms gives both numbers; INTEGRATION.md section 3 shows
+ * the two MPI calls that do.)
+ * Slot layout with the option on, per boundary: the columns f < fields of the partial sums stay
+ * (the accumulation kernels still write them; nothing reads them), and fields x K term columns
+ * follow: column fields + f * K + p holds fl(w[x] * field_f[x]) of the exchange cell x at link
+ * position p of the shared atmosphere cell, written by the one rank that owns x and +0.0 on
+ * every other rank, so the fp64 sum all-reduce delivers it exactly (x + 0 + ... + 0 = x; a
+ * -0.0 term arrives as +0.0, which the sum from +0.0 does not notice).  fcx_atmos_finish adds
+ * the K positions in order.  After fcx_run / fcx_run_atmos / fcx_run_group return, the region
+ * holds the terms (stream-ordered).  fcx_set_atmos_boundaries allocates stride = fields x
+ * (1 + K); fcx_set_atmos_shared needs a stride of at least that.  Named FCX_E_ARG errors of
+ * fcx_plan_check and fcx_commit: left_pos + the rank's own cells of that atmosphere cell >
+ * max_terms; a stride that is too small; an unsorted atmosphere map; max_terms outside 1..4096;
+ * boundary slots without this call.  Ranks that disagree on K disagree on the stride, which the
+ * signature agreement of the exchange reports on every rank. */
+int fcx_set_atmos_terms(fcx_engine *e, int32_t max_terms, int32_t left_pos);
+/* the doubles per boundary slot: the number of fcx_add_atmos_field fields, times 1 + max_terms
+ * with FCX_OPT_ATMOS_INVARIANT on and fcx_set_atmos_terms called -- for a host that owns the
+ * buffer of fcx_set_atmos_shared.  At any time; the answer follows the calls made so far. */
+int fcx_atmos_columns(const fcx_engine *e, int32_t *columns);
+/* the engines whose terms went out in ONE launch with this engine's after its last accumulation:
+ * 1 a launch of its own (fcx_run, fcx_run_atmos, an engine that exchanges by itself), n the
+ * launch shared by n engines of an fcx_run_group, 0 none (the option off, no shared cell) */
+int fcx_last_terms_group(const fcx_engine *e, int32_t *engines);
+/* 1 when FCX_OPT_ATMOS_INVARIANT is on */
+int fcx_atmos_invariant(const fcx_engine *e, int32_t *on);
 /* after the all-reduce of `shared`: boundary values -> out arrays, slots re-zeroed */
 int fcx_atmos_finish(fcx_engine *e);
 /* the accumulation of `phase` on its own (fcx_run runs it unless FCX_OPT_ATMOS_IN_RUN=0) */
@@ -766,6 +798,24 @@ enum fcx_option {
                                    the block's LDS accumulator, without the lanes' register
                                    windows (default 0).  The results are the same bits; only
                                    the time differs (bench/integrals_ab.py).  At any time.   */
+  FCX_OPT_ATMOS_INVARIANT = 26, /* atmosphere sums that do not depend on the number of ranks.
+                                   0 (default): an atmosphere cell whose exchange cells lie on
+                                   several ranks is completed by adding the ranks' partial sums
+                                   (launches, slot layout, collective and results as ever).  1:
+                                   the ranks exchange the TERMS w[x] * field[x] of such a cell,
+                                   each at its link position, and every rank adds them in
+                                   increasing x from 0.0 -- the definition above
+                                   fcx_set_atmos_map, and the bits of a one-rank engine over the
+                                   global grid, for any number of ranks.  Needs
+                                   fcx_set_atmos_terms and a sorted atmosphere map; the slots
+                                   grow to fcx_atmos_columns doubles per boundary (see
+                                   fcx_set_atmos_terms); one more launch per step (the terms,
+                                   one for all engines of an fcx_run_group), the same single
+                                   all-reduce.  On an engine with boundary slots and a shared
+                                   first or last cell, an accumulated field declared
+                                   FCX_OUT_UNREAD keeps its store (fcx_output_info says so):
+                                   the terms are formed from the stored values.  Applied at fcx_commit
+                                   (FCX_E_STATE afterwards); other values are FCX_E_ARG      */
   FCX_OPT_TILED_LAYOUT = 11   /* engine-owned mirrors tile-blocked (default 1): tiles of
                                    4096 cells, the read-only arrays' tiles interleaved in
                                    one pool and the written arrays' in another, so a wave's
