@@ -1146,6 +1146,20 @@ static int validate(fcx_engine *e) {
     if (m != FCX_NONE) NEED(s, 1, FCX_RBBR, "RBBR");
   }
 #undef NEED
+  // A regridding reads one array and writes another (basic:463-522).  Where the destination slot
+  // is bound to the source's own array -- u / v grids that ARE the t grid -- the launch would read
+  // the cells it is overwriting: refused by name, here, before any plan is built.
+  for (int s = 0; s <= kMaxTypes; ++s)
+    for (int g = 1; g <= 3; ++g)
+      for (int v = 1; v <= kNumVars; ++v)
+        for (int k = 0; k < 3; ++k) {
+          if (!((e->put_to[s][g - 1][v - 1] >> k) & 1) || k + 1 == g) continue;
+          const int src = e->buf(s, g, v);
+          if (src >= 0 && src == e->buf(s, k + 1, v))
+            return fail(FCX_E_STATE, "regridding of %s(%d,%s) to the %s grid: the destination is the source's own array "
+                                     "(grids that are one grid are not regridded)",
+                        kVarNames[v - 1], s, g == 1 ? "t" : g == 2 ? "u" : "v", k == 0 ? "t" : k == 1 ? "u" : "v");
+        }
   return FCX_OK;
 }
 

@@ -251,7 +251,10 @@ int fcx_set_corrections(fcx_engine *e, int enabled, int32_t init_date, const dou
 /* sparse_regridding_matrix (basic:117-122): 1-based, rank-local, offset-corrected links */
 int fcx_set_regrid_matrix(fcx_engine *e, int which, int64_t num_elements, const int32_t *src_index,
                           const int32_t *dst_index, const double *weight);
-/* realarray%put_to_{t,u,v}_grid of (surface_type, grid, var): bit0 t, bit1 u, bit2 v */
+/* realarray%put_to_{t,u,v}_grid of (surface_type, grid, var): bit0 t, bit1 u, bit2 v.  A
+ * regridding reads one array and writes another: a destination slot bound to the source's own
+ * array (u / v grids that ARE the t grid) is a named FCX_E_STATE error of fcx_plan_check /
+ * fcx_commit -- the launch would read the cells it is overwriting. */
 int fcx_set_put_to(fcx_engine *e, int surface_type, int grid, int var, int mask);
 /* register a type-0 output that is averaged before its oasis_put (flux_calculator.F90:
  * 911-918 early, 1001-1008 normal).  Follows the P7 trigger: only applied when the type-0

@@ -172,9 +172,9 @@ def conditioned_full(case, got, ref, t, label, tol=FP64_TOL, ulps=16, trials=8):
     base = oracle_lib.run_case(small, "c", current_step_time=t)
     move = {k: np.zeros(idx.size) for k in bad}
     eps = float(np.finfo(np.float64).eps)
-    outs = {id(small.lf.field[k]) for k in small.outputs}
     for trial in range(trials):
         c = sample_case(case, idx)
+        outs = {id(c.lf.field[k]) for k in c.outputs}
         rng = np.random.default_rng([trial, 99])
         seen = set()
         for a in c.lf.field.values():

@@ -22,8 +22,10 @@ def expand(src, dst, w, field, n_dst, dtype=np.float64):
     w[k] * field[src[k]], in double; an exchange cell without a link gets 0.0; rounded to dtype
     once."""
     acc = np.zeros(n_dst, dtype=np.float64)
-    for k in range(len(src)):
-        acc[dst[k]] = acc[dst[k]] + np.float64(w[k]) * np.float64(field[src[k]])
+    # (np.add.at is the explicit loop acc[dst[k]] = acc[dst[k]] + w[k] * field[src[k]] for k = 0, 1, ...:
+    # unbuffered, one link after the other, each product one IEEE double multiply)
+    src, dst = np.asarray(src, dtype=np.int64), np.asarray(dst, dtype=np.int64)
+    np.add.at(acc, dst, np.asarray(w, dtype=np.float64) * np.asarray(field, dtype=np.float64)[src])
     return acc.astype(dtype)
 
 

@@ -121,9 +121,25 @@ else:
     assert "plan audit" in line[0] and var in line[0] and flux in line[0], line[0]
 
 
-def test_plan_check_after_commit_is_a_state_error():
+def test_plan_check_is_repeatable():
     case = build_case("CCLM", n=16, T=1)
     e = Engine(case.lf, 1, case.methods, commit=False)
     e.plan_check()
     e.plan_check()  # repeatable: the dry plans are dropped
     e.close()
+
+
+@pytest.mark.gpu
+def test_plan_check_after_commit_is_a_state_error():
+    case = build_case("CCLM", n=16, T=1)
+    e = Engine(case.lf, 1, case.methods, commit=False)
+    try:
+        e.plan_check()
+        e.commit()
+        with pytest.raises(_lib.FcxError) as ex:
+            e.plan_check()
+        assert ex.value.status == 2 and "fcx_plan_check runs before fcx_commit" in str(ex.value), str(ex.value)
+        e.step(3, 3600)  # the refusal changed nothing: the committed engine still runs
+        assert np.all(np.isfinite(case.lf.field[(1, 1, "HSEN")]))
+    finally:
+        e.close()
