@@ -321,24 +321,25 @@ def _host(a):
     return a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()
 
 
-def _bound_cap(case, key, ref):
-    """The per-cell cap of a derived-bound field, its scale term in numpy from the inputs."""
+def _bound_cap(case, key, ref, eps=EPS):
+    """The per-cell cap of a derived-bound field, its scale term in numpy (float64) from the
+    inputs; eps = the arithmetic's epsilon (2**-52, or 2**-23 for assert_tight_f32)."""
     s, g, name = key
     f = lambda v: np.asarray(_host(case.lf.field[(s, g, v)]), dtype=np.float64)  # noqa: E731
     ref = np.abs(np.asarray(ref, dtype=np.float64))
     if name == "QSUR":
-        return QSUR_CAP * EPS * ref
+        return QSUR_CAP * eps * ref
     vel = np.sqrt(f("UATM") * f("UATM") + f("VATM") * f("VATM"))
     if name == "HSEN":
         a = f("AMOI" if _method(case, s, g, name) == "CCLM" else "CHEA")
         ps, ts = f("PSUR"), f("TSUR")
         rate = a * np.maximum(vel, _UMIN) * ps / (_RD * ts * (1.0 + (_RV / _RD - 1.0) * f("QATM")))
         ef = (ps / f("PATM")) ** (_RD / _CP)
-        return HSEN_CAP[0] * EPS * np.abs(rate * _CP * f("TATM") * ef) + HSEN_CAP[1] * EPS * ref
+        return HSEN_CAP[0] * eps * np.abs(rate * _CP * f("TATM") * ef) + HSEN_CAP[1] * eps * ref
     if name == "MEVA":
         ts = f("TSUR")
         q_w = 0.62197 * (6.1078E+02 * np.exp(17.269 * (ts - 273.15) / (ts - 35.86))) / 1.013E+05
-        return MEVA_RCO_CAP[0] * EPS * np.abs(1.225 * 1.15E-03 * vel * q_w) + MEVA_RCO_CAP[1] * EPS * ref
+        return MEVA_RCO_CAP[0] * eps * np.abs(1.225 * 1.15E-03 * vel * q_w) + MEVA_RCO_CAP[1] * eps * ref
     raise AssertionError(f"{key}: no derived bound")
 
 
@@ -466,6 +467,144 @@ def assert_tight(case, got, ref, t, label, report=True):
         out["%d:%d:%s" % key] = rec
     if report:
         write_report("ulp_gate_" + "".join(c if c.isalnum() or c in "-_." else "_" for c in label), out)
+    if problems:
+        raise AssertionError(f"{label}: " + "; ".join(problems))
+    return out
+
+
+# --------------------------------------------------------------------------------------
+# Tight gates of the plain fp32 engines (FCX_PRECISION_F32 without FCX_OPT_F32_MATH)
+# --------------------------------------------------------------------------------------
+EPS32 = 2.0 ** -23
+
+
+def bits_equal32(a, b):
+    """bits_equal for float32 arrays, through uint32 views (-0.0 != +0.0, NaN matches NaN)."""
+    a, b = np.asarray(a), np.asarray(b)
+    assert a.dtype == np.float32 and b.dtype == np.float32, (a.dtype, b.dtype)
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    if a.shape != b.shape:
+        raise AssertionError(f"shape {a.shape} != {b.shape}")
+    na, nb = np.isnan(a), np.isnan(b)
+    return (na & nb) | (~na & ~nb & (a.view(np.uint32) == b.view(np.uint32)))
+
+
+def assert_tight_f32(case32, got, t, label, report=True):
+    """assert_tight for the plain fp32 engine: every cell of every output of an fp32 case
+    (fcx.synthetic.as_dtype(case, "float32"); for device-resident runs its host twin) in one of the
+    same gates, eps = eps32 = 2**-23.  The reference is not an oracle build but tests/f32_expect.py,
+    the float32 restatement of fcx_physics.h at R = float and of the kernel's loop glue, pinned bit
+    for bit to the header's host build by tests/test_f32_expect.py; its three transcendental sites
+    take the CORRECTLY ROUNDED single exp and log (the double function rounded once).  got = the
+    device's float32 outputs; classes from gate_of (it refuses what it refuses for fp64);
+    "bit-identical" = equal uint32 views (-0.0 != +0.0), NaN cells equal NaN cells.
+
+    exact         bit-identical to f32_expect.expected(case32, t).  RBBR, RSDR, the TSUR average,
+                  HSEN/UMOM/VMOM of RCO, every 'zero', their averages.
+    seeded-exact  bit-identical to expected(..., qsur = the device's own QSUR arrays).
+                  MEVA/UMOM/VMOM of CCLM and MOM5, HLAT over such a MEVA, their averages.
+    construction  from the device's own stored values, for EVERY such field whatever its class,
+                  no tolerance: HLAT == MEVA_dev * float32(L), and every type-0 average ==
+                  acc = float32(0); acc = acc + x_s * FARE_s in type order in float32.
+    derived-bound per cell against expected() with the correctly rounded sites, the scale terms
+                  in numpy float64 from the inputs, as assert_tight:
+                  QSUR (CCLM)       |d| <= 8 eps32 |ref|
+                  HSEN (CCLM, MOM5) |d| <= 4 eps32 |F c_p T_a EF| + 4 eps32 |ref|
+                  MEVA (RCO)        |d| <= 6 eps32 |rho_a c_aw vel q_w| + 4 eps32 |ref|
+
+    The caps are assert_tight's, and its derivation carries over unit for unit (eps -> eps32)
+    under one ASSUMPTION: the device's single-precision exp and log are within 1 ulp.  That is the
+    figure of the HIP math API's accuracy table for expf and logf; the ROCm installation this was
+    written against carries neither that table nor a figure in its headers, so it is stated here
+    and not cited from a file.  The reference side is better than assert_tight's (a correctly
+    rounded site, 0.5 ulp, where glibc's is within 1), so two site results differ by at most
+    1.5 eps32 relative, inside the 2 eps the derivation uses.  Its one side condition, "the error
+    of pow_exner's argument y log x is below 1e-2 eps absolute", holds in float32: x = ps/pa in
+    (1, 1.02) gives log x < 0.02, whose ulp is 2^-29 = 1.9e-9; two logs within 1 ulp differ by
+    that, times y = 0.2856: 5.3e-10, and the product's rounding (|y log x| < 0.0057, ulp 4.7e-10)
+    can move it by one more ulp: 1.0e-9 < 1e-2 eps32 = 1.2e-9.  The caps are never fitted to a
+    device output; the measured worst ratios go into the report.
+
+    Returns and writes (f32_gate_<label>.json, also when it fails) the report of assert_tight and
+    raises an AssertionError that lists every failing field with its gate and cell count."""
+    import f32_expect
+
+    assert set(got) == set(case32.outputs), f"{label}: outputs {sorted(set(got) ^ set(case32.outputs))} on one side only"
+    gates = {k: gate_of(case32, k) for k in case32.outputs}  # raises for an unclassified field
+    for k, v in got.items():
+        assert np.asarray(v).dtype == np.float32, f"{label}: {k} is {np.asarray(v).dtype}, not the device's float32"
+    expect = f32_expect.expected
+    ref = expect(case32, t)
+    dev = {id(case32.lf.field[k]): np.asarray(got[k]) for k in got}
+
+    def value(k):
+        v = dev.get(id(case32.lf.field[k]))
+        v = np.asarray(_host(case32.lf.field[k])) if v is None else v
+        assert v.dtype == np.float32, (k, v.dtype)
+        return v
+
+    seeded = None
+    if SEEDED in gates.values():
+        seeded = expect(case32, t, qsur={k: got[k] for k in got if k[2] == "QSUR"})
+    out, problems = {}, []
+
+    def fail(rec, key, gate, ok, what):
+        idx = np.nonzero(~ok)[0]
+        rec["failed_cells"][gate] = rec["failed_cells"].get(gate, 0) + int(idx.size)
+        g = np.asarray(got[key])
+        problems.append(f"{key} [{gate}] {what}: {idx.size} of {ok.size} cells, first {idx[:6].tolist()}, "
+                        f"got {g[idx[:3]].tolist()}")
+
+    for key, gate in gates.items():
+        s, g, name = key
+        x, r = np.asarray(got[key]), ref[key]
+        same = bits_equal32(x, r)
+        rec = {"gate": gate, "cells": int(x.size), "bit_identical_share": float(same.mean()) if x.size else 1.0,
+               "worst_ratio": 0.0, "failed_cells": {}}
+        covered = np.zeros(x.shape, dtype=bool)
+        if gate == EXACT:
+            covered[:] = True
+            if not same.all():
+                fail(rec, key, gate, same, "differs from the float32 restatement")
+        elif gate == SEEDED:
+            covered[:] = True
+            ok = bits_equal32(x, seeded[key])
+            rec["bit_identical_share"] = float(ok.mean()) if x.size else 1.0
+            if not ok.all():
+                fail(rec, key, gate, ok, "differs from the float32 restatement seeded with the device's QSUR")
+        elif gate == BOUND:
+            covered[:] = True
+            x64, r64 = x.astype(np.float64), r.astype(np.float64)
+            cap = _bound_cap(case32, key, r64, eps=EPS32)
+            d = np.abs(x64 - r64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                ratio = np.where(d == 0.0, 0.0, d / cap)
+            ratio = np.where(np.isnan(x64) & np.isnan(r64), 0.0, ratio)
+            ratio = np.where(np.isnan(ratio), np.inf, ratio)  # NaN on one side only
+            ok = ratio <= 1.0
+            rec["worst_ratio"] = float(ratio.max(initial=0.0))
+            if not ok.all():
+                fail(rec, key, gate, ok, f"over its cap (worst ratio {rec['worst_ratio']:.3g})")
+        # by construction, from the device's own values, in float32
+        if s >= 1 and name == "HLAT" and _method(case32, s, g, name) in ("water", "ice"):
+            covered[:] = True
+            L = np.float32(_LV if _method(case32, s, g, name) == "water" else _LS)
+            built = value((s, 1, "MEVA")) * L
+            ok = bits_equal32(x, built)
+            if not ok.all():
+                fail(rec, key, BUILT, ok, f"is not MEVA_dev * float32({L})")
+        if s == 0:
+            covered[:] = True
+            acc = np.zeros(x.shape, np.float32)
+            for i in range(1, case32.num_surface_types + 1):
+                acc = acc + value((i, g, name)) * np.asarray(_host(case32.lf.field[(i, g, "FARE")]))
+            ok = bits_equal32(x, acc)
+            if not ok.all():
+                fail(rec, key, BUILT, ok, "is not the in-order float32 sum of x_s * FARE_s of the device's x_s")
+        assert covered.all(), f"{label}: {key} has cells in no gate"
+        out["%d:%d:%s" % key] = rec
+    if report:
+        write_report("f32_gate_" + "".join(c if c.isalnum() or c in "-_." else "_" for c in label), out)
     if problems:
         raise AssertionError(f"{label}: " + "; ".join(problems))
     return out

@@ -3,7 +3,10 @@ max/percentile error vs oracle").  The fp32 engine (FCX_PRECISION_F32) stores an
 in float; its outputs are compared with the fp64 oracle run on the SAME inputs (the float32
 arrays widened exactly), so the reported error is the error of fp32 arithmetic alone.
 Gate: tests/parity.py FP32_NORM_GATE on the norm-wise error (report, not a parity claim);
-fp64 parity is tests/test_gpu_parity.py."""
+fp64 parity is tests/test_gpu_parity.py.  Beside it every test that goes through run_fp32 / check
+holds the same outputs cell by cell to parity.assert_tight_f32 (the float32 restatement
+tests/f32_expect.py; tests/test_gpu_f32_gate.py), except the staged regridding case: a regridded
+field has no gate there, as in assert_tight."""
 import json
 import os
 
@@ -11,7 +14,7 @@ import numpy as np
 import pytest
 
 import oracle_lib
-from parity import FP32_NORM_GATE, error_report
+from parity import FP32_NORM_GATE, assert_tight_f32, error_report
 
 pytestmark = pytest.mark.gpu
 
@@ -34,7 +37,14 @@ def run_fp32(case, options=None):
     eng.close()
     for k in c32.outputs:
         assert c32.lf.field[k].dtype == np.float32
+    tight_f32(c32, f"{case.name}_n{case.grid_size[0]}_{options}")
     return got, ref
+
+
+def tight_f32(c32, label, t=STEP_T):
+    """the tight fp32 gates on the outputs the engine left in the case's own float32 arrays"""
+    return assert_tight_f32(c32, {k: np.array(c32.lf.field[k], copy=True) for k in c32.outputs}, t, label,
+                            report=False)
 
 
 def check(got, ref, label):
@@ -301,3 +311,4 @@ def test_fp32_fused_accumulation(variant, mode, lengths):
     c64 = as_dtype(c32, "float64")
     ref = oracle_lib.run_case(c64, "c", current_step_time=STEP_T + 3600)
     check({k: np.array(c32.lf.field[k], dtype=np.float64) for k in c32.outputs}, ref, f"{variant} fused fp32")
+    tight_f32(c32, f"{variant} fused fp32 {mode} {lengths}", t=STEP_T + 3600)

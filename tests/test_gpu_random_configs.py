@@ -171,8 +171,10 @@ def test_random_configuration_and_transport(seed):
 @pytest.mark.parametrize("seed", range(SEED_BASE, SEED_BASE + 32))
 def test_random_configuration_fp32(seed):
     """The fp32 engine on a random configuration, against the fp64 oracle on the same
-    (fp32-rounded) inputs: the norm-wise fp32 gate of tests/parity.py."""
-    from parity import FP32_NORM_GATE
+    (fp32-rounded) inputs: the norm-wise fp32 gate of tests/parity.py; and cell by cell the tight
+    fp32 gates (parity.assert_tight_f32).  The tight gates leave out a configuration only where
+    parity.gate_of refuses one of its fields, i.e. exactly where the fp64 assert_tight would."""
+    from parity import FP32_NORM_GATE, assert_tight_f32, gate_of
     from fcx.synthetic import as_dtype
 
     spec = draw_case(200 + seed)
@@ -184,7 +186,19 @@ def test_random_configuration_fp32(seed):
                  averages=c32.averages)
     eng.step(PHASE_ALL, STEP_T)
     got = {k: np.array(c32.lf.field[k], dtype=np.float64) for k in c32.outputs}
+    got32 = {k: np.array(c32.lf.field[k], copy=True) for k in c32.outputs}
     eng.close()
+    try:
+        for k in c32.outputs:
+            gate_of(c32, k)
+        refused = None
+    except AssertionError as ex:
+        refused = str(ex)
+    if refused is None:  # every configuration the fp64 gates accept is held: none left out
+        assert_tight_f32(c32, got32, STEP_T, f"random_fp32_seed{seed}", report=False)
+    else:
+        assert "more than once" in refused or "no gate" in refused or "in none of the gates" in refused \
+            or "'copy' of a 'copy'" in refused, refused
     # (a few cells of 1-3 with HSEN cancelling in fp32 exceed the norm-wise gate: seed 24)
     conditioned_parity(lambda: as_dtype(as_dtype(build_case(**spec), "float32"), "float64"), got, ref,
                        label=f"seed {seed}: {spec} (fp32)", tol=FP32_NORM_GATE, eps=2.0 ** -23, normwise=True)
