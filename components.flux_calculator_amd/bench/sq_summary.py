@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-wave SQ counters of the group launches from two rocprofv3 --pmc passes
-(bench/r05_pmc.sh: <dir>/sq and <dir>/sq2), means over the group-kernel dispatches
+(<dir>/sq and <dir>/sq2), means over the group-kernel dispatches
 (measurement tool; the same rule as profiles/r04/sq_counters.json).
 
   python sq_summary.py DIR [DIR ...] > sq_counters.json
@@ -45,7 +45,7 @@ def main():
                 "per_wave": {n: round(c.get(n, 0) / w, 1) for n in (
                     "SQ_INSTS_VALU", "SQ_INSTS_SALU", "SQ_INSTS_LDS", "SQ_INSTS_VMEM_RD", "SQ_INSTS_VMEM_WR",
                     "SQ_LDS_BANK_CONFLICT", "SQ_WAIT_INST_LDS")}}
-    out["_source"] = ("bench/r05_pmc.sh: rocprofv3 --pmc, two passes of 8 SQ counters per workload (bench.py "
+    out["_source"] = ("rocprofv3 --pmc, two passes of 8 SQ counters per workload (bench.py "
                       "--steps 20 --warmup 5, main workload only); means over the group launches")
     print(json.dumps(out, indent=1))
 

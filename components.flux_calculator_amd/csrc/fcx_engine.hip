@@ -445,7 +445,6 @@ struct fcx_engine {
   bool staging = true;
   bool deferred_scatter = false;        // FCX_OPT_DEFERRED_SCATTER: downloads scattered at fcx_synchronize
 #ifdef FCX_AB_BUILD
-  bool ab_fixup_each = false;
   bool ab_no_head = false;
 #endif
   int host_threads = 0;                 // FCX_OPT_HOST_THREADS (0: default_host_threads)
@@ -1198,9 +1197,9 @@ static void plan_fused_atmos(fcx_engine *e, Plan &pl, uint32_t stages, int phase
   // (segments longer than half a tile, several hundred exchange cells per atmosphere cell,
   // go to atmos_kernel in every precision: one lane summing a long segment would hold up its
   // whole wave)
-  // (the maps its launches read: compact_map)
-  const bool maps = (!compact_map(e->f32, true) || e->d_atm_seg) && (!compact_map(e->f32, false) || e->d_atm_seg) &&
-                    (compact_map(e->f32, true) || e->d_atm_idx) && (compact_map(e->f32, false) || e->d_atm_idx);
+  // (the maps its launches read, compact_map: the compacted map, and in an fp64 engine, whose
+  // launches with crossing records read it, the index)
+  const bool maps = e->d_atm_seg && (e->f32 || e->d_atm_idx);
   if (!pl.variant || !maps || e->atm_maxseg > kTile / 2 || e->any_regrid || phase <= 0 ||
       phase >= 1000 || !e->specialize)
     return;
@@ -1283,10 +1282,7 @@ static int plan_fused_records(fcx_engine *e, Plan &pl, uint32_t stages, int phas
   pl.rec_remap = pl.rec_group = -1;
   Params &P = pl.host;
   for (int k = 0; k < 6; ++k) P.rec_pos[k] = -1;
-#ifndef FCX_FUSE_RECORDS  // A/B builds: 0 = remap records only from the packing pass
-#define FCX_FUSE_RECORDS 1
-#endif
-  if (!FCX_FUSE_RECORDS || !pl.variant || e->T != 1 || e->f32 || !e->specialize || e->any_regrid || phase <= 0 || phase >= 1000 ||
+  if (!pl.variant || e->T != 1 || e->f32 || !e->specialize || e->any_regrid || phase <= 0 || phase >= 1000 ||
       e->remap_pack == 0 || e->launch.cells_per_thread != 2 || !e->aligned16 || !P.merged_uv || P.n_max <= 0)
     return FCX_OK;
   const TypeParams &tp = P.type[0];
@@ -2191,14 +2187,10 @@ constexpr size_t kSlabBytes = size_t(32) << 20;  // smallest slab (one Baltic-si
 // link is shared with the machine's other GPUs' jobs (bench/d2h_flags_probe.hip,
 // zc_flags_probe.hip, numa_probe.hip, profiles/r06/probes/).  Portable memory never measured
 // slower and is what a multi-device host needs.
-#ifndef FCX_PIN_PORTABLE  // A/B builds: 0 = the pre-round-6 flags (hipHostMallocDefault / Mapped)
-#define FCX_PIN_PORTABLE 1
-#endif
-#ifndef FCX_PIN_NONCOHERENT  // A/B builds: 1 = mapped non-coherently (the GPU's L2 may hold host lines
-#define FCX_PIN_NONCOHERENT 0  // within a kernel; made visible at the kernel boundaries)
-#endif
-constexpr unsigned kHostPinFlags = (FCX_PIN_PORTABLE ? hipHostMallocPortable : hipHostMallocDefault) |
-                                   (FCX_PIN_NONCOHERENT ? hipHostMallocNonCoherent : 0u);
+// Coherent mapping: a non-coherent mapping (the GPU's L2 may hold host lines within a kernel)
+// ran the Baltic zero-copy step the same within the link's noise
+// (profiles/r06/probes/pin_noncoherent_ab.jsonl).
+constexpr unsigned kHostPinFlags = hipHostMallocPortable;
 constexpr size_t kBlockAlign = 256;
 
 struct HostSlab {
@@ -2462,9 +2454,6 @@ static int span_copy(fcx_engine *e, std::vector<int> ids, bool h2d, hipStream_t 
 // pool instead of 10-20 separate streams: 6.35 vs 5.8 TB/s for the CCLM/MOM5/RCO access
 // shapes (bench/layout_probe.hip; one mixed pool 6.28, a pool with unused slots between the
 // streamed arrays 6.1, tiles of 2048 / 8192 cells 6.25 / 6.31).
-#ifndef FCX_TILED_ATM  // A/B builds: 0 keeps the atmosphere output mirrors contiguous
-#define FCX_TILED_ATM 1
-#endif
 static uint32_t phase_stages(int phase);
 static int alloc_tiled(fcx_engine *e) {
   static const int kOut[] = {FCX_QSUR, FCX_MEVA, FCX_HLAT, FCX_HSEN, FCX_RBBR, FCX_UMOM, FCX_VMOM, FCX_RSDR};
@@ -2970,17 +2959,10 @@ static bool remap_packs(const fcx_engine *e, const fcx_engine::Remap &rm, int nf
   return e->remap_pack == 1 || (e->remap_pack == 2 && nf >= 2 && rm.scatter > kPackScatter);
 }
 
-// elements per packed record of nf fields: a whole number of 16-B vectors (A/B builds
-// with FCX_REC_POW2: a power of two, so that no record straddles a 64-B boundary)
+// elements per packed record of nf fields: a whole number of 16-B vectors
 static int rec_width(const fcx_engine *e, int nf) {
   const int v = (int)(16 / e->esize);
-#if defined(FCX_REC_POW2) && FCX_REC_POW2
-  int p = v;
-  while (p < nf) p *= 2;
-  return p;
-#else
   return (nf + v - 1) / v * v;
-#endif
 }
 
 // distinct 64-B field segments per link over a sample of 256-destination blocks
@@ -3195,7 +3177,7 @@ static int commit_corrections(fcx_engine *e) {
 }
 
 // the compacted atmosphere map, and the first cell's atmosphere cell of every wave tile: the
-// crossing records' entry, where launches with records read the compacted map
+// crossing records' entry, where launches with records read the compacted map (fp32 engines)
 static int commit_compact_map(fcx_engine *e) {
   const int64_t nx = (int64_t)e->atm_idx.size(), nw = (nx + 31) / 32;
   std::vector<uint32_t> seg((size_t)(2 * nw + 1), 0u);  // bits, then prefix counts (int32)
@@ -3217,7 +3199,7 @@ static int commit_compact_map(fcx_engine *e) {
   HIP_TRY(hipMemcpy(e->d_atm_seg, seg.data(), head, hipMemcpyHostToDevice));
   if (!atm.empty())
     HIP_TRY(hipMemcpy((char *)e->d_atm_seg.p + head, atm.data(), atm.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-  if (!compact_map(e->f32, false)) return FCX_OK;
+  if (!e->f32) return FCX_OK;
   const int64_t tc = (int64_t)fused_cpl(e->f32, e->wide()) * 64, nt = (nx + tc - 1) / tc;
   std::vector<int32_t> a0((size_t)nt);
   for (int64_t t = 0; t < nt; ++t) a0[(size_t)t] = e->atm_idx[(size_t)(t * tc)];
@@ -3232,12 +3214,11 @@ static int commit_maps(fcx_engine *e) {
   if (e->n_atmos < 0) return FCX_OK;
   if (int r = e->atm.upload(false, !e->atm_contiguous)) return r;
   if (!e->atm_contiguous || e->atm_idx.empty()) return FCX_OK;
-  // the per-cell index, where some fp64 launch reads it
-  if (!(compact_map(e->f32, true) && compact_map(e->f32, false)))
+  // which launch reads which map: compact_map.  The per-cell index for the fp64 launches with
+  // crossing records; the compacted map for every engine (fp32 launches, fp64 halo launches)
+  if (!e->f32)
     if (int r = e->d_atm_idx.upload(e->atm_idx)) return r;
-  // the compacted map, where some launch reads it
-  if (compact_map(e->f32, true) || compact_map(e->f32, false))
-    if (int r = commit_compact_map(e)) return r;
+  if (int r = commit_compact_map(e)) return r;
   // the fused path's crossing records
   const int64_t tiles = (e->n[0] + kTile - 1) / kTile;
   HIP_TRY(e->d_atm_xrec.alloc((size_t)std::max<int64_t>(tiles, 1) * kXRec * sizeof(double)));
@@ -3259,11 +3240,11 @@ static int commit_atmos_outputs(fcx_engine *e) {
     atm_ext = atm_ext || f.m.external;
     if (!f.m.external) need += (mirror_bytes(f.m.n, e->esize) + 255) / 256 * 256;
   }
-  // tile-blocked outputs (with the field mirrors, FCX_TILED_ATM): the fields' tiles of 4096
+  // tile-blocked outputs (with the field mirrors): the fields' tiles of 4096
   // atmosphere cells side by side, so the fused kernel's segment-end stores of a wave land
   // in one region instead of one per field
   const int64_t nfa = (int64_t)e->atm_fields.size();
-  if (FCX_TILED_ATM && e->tpad && !atm_ext && nfa >= 2 && e->n_atmos > 0) {
+  if (e->tpad && !atm_ext && nfa >= 2 && e->n_atmos > 0) {
     const int64_t tiles = (e->n_atmos + kLayoutTile - 1) / kLayoutTile;
     const size_t soa_bytes = (size_t)tiles * nfa * kLayoutTile * e->esize;
     e->atm_out_tpad = (nfa - 1) * kLayoutTile;
@@ -3459,10 +3440,6 @@ static int copy_bufs(fcx_engine *e, const std::vector<int> &ids, bool h2d, std::
   return stage_out(e, xs, e->stream);
 }
 
-#ifndef FCX_ZC_ONE_CELL  // A/B builds: 0 keeps 16-B (2-cell) lanes in zero-copy launches
-#define FCX_ZC_ONE_CELL 1
-#endif
-
 // halo lanes of a fused launch of plan pl over the whole grid (0: crossing records and the
 // fix-up launch): one surface type, on a map whose segments are short enough that `halo`
 // lanes of the next tile's head (at most 1/16 of a wave) cover every crossing
@@ -3470,7 +3447,7 @@ static int full_range_halo(const fcx_engine *e, const Plan *pl) {
   const int cpl = fused_cpl(e->f32, e->wide());
   const int h = (e->atm_maxseg - 1 + cpl - 1) / cpl;
   if (e->atm_halo && e->atm_crossings > 0 &&
-      (pl->host.num_types == 1 || (FCX_HALO_RAVG && pl->host.ravg_on)) && h >= 1 && h <= (cpl == 4 ? 2 : 4))
+      pl->host.num_types == 1 && h >= 1 && h <= (cpl == 4 ? 2 : 4))
     return h;
   return 0;
 }
@@ -3490,7 +3467,7 @@ static LaunchConfig plan_launch(fcx_engine *e, Plan *pl, int64_t lo, int64_t hi,
   // waves), unless this launch also feeds the fused accumulation or writes remap records
   // (both 2 cells per lane).  Kernel 80.5 -> 72.6-75.2 us per CCLM step at 32,768 cells
   // (profiles/r03/zc_shape_ab/; one-wave workgroups on top changed nothing)
-  if (FCX_ZC_ONE_CELL && e->zc_active && !pl->atm_fused && pl->host.rec == nullptr) lc.cells_per_thread = 1;
+  if (e->zc_active && !pl->atm_fused && pl->host.rec == nullptr) lc.cells_per_thread = 1;
   lc.merged = pl->host.merged_uv != 0;
   lc.variant = (e->specialize && lc.merged) ? pl->variant : 0;
   lc.f32 = e->f32;
@@ -4713,13 +4690,6 @@ static int launch_group(const GroupLaunchMember *mem, int nm) {
   AtmosFused fx[kMaxGroup];
   int64_t fx_n[kMaxGroup];
   int nfx = 0;
-#ifdef FCX_AB_BUILD
-  if (mem[0].e->ab_fixup_each) {
-    for (int k = 0; k < nm; ++k)
-      if (int r2 = launch_fixup(mem[k].e, mem[k].pl, mem[k].lc)) return r2;
-    return FCX_OK;
-  }
-#endif
   for (int k = 0; k < nm; ++k) {
     const GroupLaunchMember &m = mem[k];
     if (m.e->atm_crossings > 0 && m.lc.halo == 0) {
@@ -5290,9 +5260,6 @@ extern "C" int fcx_set_option(fcx_engine *e, int option, int64_t value) {
     case 98:  // measurement builds: no head records (wrong crossing values; cost of the stores)
       e->ab_no_head = value != 0;
       for (auto &kv : e->plans) kv.second.af.xrec_on = !e->ab_no_head && e->atm_crossings > 0;
-      return FCX_OK;
-    case 99:  // measurement builds: the group's fix-ups as one launch per member (old path)
-      e->ab_fixup_each = value != 0;
       return FCX_OK;
 #endif
     default:

@@ -33,28 +33,17 @@
 #ifndef FCX_WAVE_TRACE
 #define FCX_WAVE_TRACE 0
 #endif
-// halo tiles also for the multi-type kernel with register averages (A/B)
-#ifndef FCX_HALO_RAVG
-#define FCX_HALO_RAVG 0
-#endif
-// one s_waitcnt vmcnt(0) after a type's input loads in the single-type (TM = 1) kernels, in
-// straight-line code before the first flux block, so that no flux block waits for the stores
-// of the blocks before it (fcx_kernels.hip, process; 0 = A/B: the compiler's own waits)
-#ifndef FCX_INPUT_WAIT
-#define FCX_INPUT_WAIT 1
-#endif
-// the compacted map's dependent load of the segments' atmosphere cells issued right behind
-// that wait, in flight during the flux arithmetic (fcx_kernels.hip, atmos_tile; needs
-// FCX_INPUT_WAIT): 0 = after the flux pass
-#ifndef FCX_EARLY_SEG_ATM
-#define FCX_EARLY_SEG_ATM 0
-#endif
-// the fp64 launches' exchange -> atmosphere map (fp32 launches always read the compacted
-// one): 0 = a 4-B index per cell; 1 = the compacted map in halo launches, the index in
-// launches with crossing records; 2 = the compacted map in every launch
-#ifndef FCX_F64_COMPACT
-#define FCX_F64_COMPACT 1
-#endif
+// Rules of the fused kernels that are stated where they apply, with their evidence:
+//  - halo tiles are for the single-type (T = 1) launches only; the multi-type kernel with
+//    register averages keeps crossing records (with halo tiles its T = 2 step took +3.9 %,
+//    DESIGN.md section 3, profiles/r06/probes/halo_t2_ab.json)
+//  - the single-type (TM = 1) kernels wait once, s_waitcnt vmcnt(0), after a type's input loads,
+//    in straight-line code before the first flux block, so that no flux block waits for the
+//    stores of the blocks before it (fcx_kernels.hip, process / wait_inputs; profiles/r09/isa/)
+//  - the compacted map's dependent load of the segments' atmosphere cells follows the flux pass
+//    (fcx_kernels.hip, atmos_tile; issued right behind that wait it gained nothing: DESIGN.md
+//    section 3, "Current numbers")
+//  - which fused launches read the compacted exchange -> atmosphere map: compact_map() below
 
 namespace fcx {
 
@@ -118,10 +107,6 @@ enum WantBit : uint32_t {
   W_RBBR = 1u << 0, W_HLAT = 1u << 1, W_HSEN = 1u << 2, W_UMOM = 1u << 3, W_VMOM = 1u << 4,
   W_QSUR_U = 1u << 5, W_QSUR_V = 1u << 6
 };
-// the unstored-output path in the kernels (A/B builds: 0 = every computed output is stored)
-#ifndef FCX_SKIP_STORES
-#define FCX_SKIP_STORES 1
-#endif
 // Which kernel family may leave out the store of a wanted output (TypeParams::want) -- ONE rule
 // for the kernels (process: elsewhere the byte is a compile-time zero and the code is the stored
 // path's) and for the planner (build_plan: elsewhere an FCX_OUT_UNREAD output with a consumer in
@@ -139,21 +124,11 @@ enum WantBit : uint32_t {
 // (f32: the storage type; an fp32 engine computing in double, FCX_OPT_F32_MATH, goes by the fp32
 // engine's rule: at its two cells per lane the halo kernels hold no scratch with the path.)
 constexpr bool skip_family(bool f32, int variant, bool ravg, bool tm1, bool merged, bool halo) {
-  if (!FCX_SKIP_STORES) return false;
   if (ravg) return false;
   if (!f32 && variant == 1 && tm1 && halo) return false;
   if (!f32 && variant == 0 && !tm1 && !ravg && merged) return false;
   return true;
 }
-// the destination stores of the received fields' gather (fcx_kernels.hip, receive_inject_kernel):
-// 0 = plain (the flux pass reads the arrays right after), 1 = non-temporal (A/B builds)
-#ifndef FCX_RECV_NT
-#define FCX_RECV_NT 0
-#endif
-// the wave-uniform inputs in the kernels (A/B builds: 0 = every input is an array)
-#ifndef FCX_CONST_UNIFORM
-#define FCX_CONST_UNIFORM 1
-#endif
 // Which kernel family takes wave-uniform inputs -- ONE rule for the kernels (uniform_inputs<>,
 // the template arguments of process) and for the planner (build_plan, with the variant and
 // register-average mode its launch will be instantiated with): a set cmask bit in a launch of
@@ -162,7 +137,7 @@ constexpr bool skip_family(bool f32, int variant, bool ravg, bool tm1, bool merg
 // register-average kernel takes them, in any precision: a namelist constant of a multi-type
 // launch, fused or not, is an engine-filled array.)
 constexpr bool uniform_family(bool f32, int variant, bool ravg) {
-  return FCX_CONST_UNIFORM && !f32 && !ravg && (variant == 0 || variant == 1);
+  return !f32 && !ravg && (variant == 0 || variant == 1);
 }
 // The kernels read a type's method bytes as ONE aligned 64-bit word (m_qsur[0] in the low
 // byte ... m_rbbr in the high one) and bias_adds with its padding as the next 64-bit word
@@ -205,10 +180,7 @@ struct AvgRegs {
 // element (j >> kLayoutShift) * tile_stride + (j & (kLayoutTile - 1)) of its buffer; the
 // kernels get tpad = tile_stride - kLayoutTile and address base + j + (j >> kLayoutShift) * tpad
 // (tpad = 0: plain contiguous arrays).  Chunk boundaries of a tiled engine are whole tiles.
-#ifndef FCX_LAYOUT_SHIFT  // A/B builds: tiles of 2^shift cells (4096 measured best)
-#define FCX_LAYOUT_SHIFT 12
-#endif
-constexpr int kLayoutShift = FCX_LAYOUT_SHIFT;
+constexpr int kLayoutShift = 12;  // tiles of 2^shift cells (4096 measured best)
 constexpr int64_t kLayoutTile = int64_t(1) << kLayoutShift;
 __host__ __device__ inline int64_t tiled(int64_t j, int64_t tpad) { return j + (j >> kLayoutShift) * tpad; }
 // Element of atmosphere cell a in an atmosphere output array.  Two layouts: the arrays of
@@ -336,10 +308,11 @@ constexpr int kFusedFields = 6;
 constexpr int kRecHead = 4;     // head products kept per crossing record (longer heads: recomputed)
 constexpr int kXRec = 32;       // doubles per crossing record (256 B, two lines)
 constexpr int kTile = 128;  // cells per wave iteration (64 lanes x 2)
-// the fused launches that read the compacted map (AtmosFused::seg_*) rather than idx
-constexpr bool compact_map(bool f32, bool halo) {
-  return f32 || FCX_F64_COMPACT == 2 || (FCX_F64_COMPACT == 1 && halo);
-}
+// the fused launches that read the compacted map (AtmosFused::seg_*) rather than idx: the fp32
+// launches and the fp64 halo launches; fp64 launches with crossing records read the 4-B index per
+// cell (the compacted map there lost: T = 2 +1.1 %, T = 1 on the periodic map +2.1 %,
+// profiles/r05/f64seg2/; an index in the halo launches too lost 0.1 - 0.7 %, profiles/r05/f64seg/)
+constexpr bool compact_map(bool f32, bool halo) { return f32 || halo; }
 struct AtmosFused {
   // the exchange -> atmosphere map of a contiguous (sorted) map, compacted (round 5): bit x of
   // seg_bits[x / 32] is set where exchange cell x starts a segment (its atmosphere cell
@@ -391,22 +364,17 @@ struct FinishGroup {
   int32_t nb[kMaxGroup];
   AtmosArgs a[kMaxGroup];
 };
-// cells per lane of the fp32 engine's fused kernels (16-B lanes of 4 floats; A/B builds: 2,
-// 8-B lanes of 2 floats in 128-cell tiles like the fp64 kernels, half the registers per lane)
-#ifndef FCX_F32_CPL
-#define FCX_F32_CPL 4
-#endif
-constexpr int kF32Cpl = FCX_F32_CPL;
+// cells per lane of the fp32 engine's fused kernels (16-B lanes of 4 floats; 2, 8-B lanes of
+// 2 floats in 128-cell tiles like the fp64 kernels and half the registers per lane, took the
+// group step from 0.441 to 0.460 ms: profiles/README.md, round-4 index, profiles/r04/f32c2/)
+constexpr int kF32Cpl = 4;
 // ... and of the wide fused kernels (FCX_OPT_F32_MATH): 2, 8-B lanes of 2 floats in 128-cell
 // tiles.  Their step is bound by the fp64 arithmetic, not by memory: four cells per lane hold
 // 172-197 VGPRs (2 waves per SIMD) and ran the T = 1 group launch in 0.811 ms, two cells per
 // lane fit the 128 of 4 waves and ran it in 0.688 ms (profiles/r13/f32_math/ab/).  The tile
 // size is all that differs from the fp32 engine's launches: the compacted map, the crossing
 // records (indexed by this tile), halo lanes and the fix-up go by it.
-#ifndef FCX_WIDE_CPL
-#define FCX_WIDE_CPL 2
-#endif
-constexpr int kWideCpl = FCX_WIDE_CPL;
+constexpr int kWideCpl = 2;
 // cells per lane of a fused launch: fp64 2, fp32 kF32Cpl, fp32 computing in double kWideCpl
 constexpr int fused_cpl(bool f32, bool wide) { return !f32 ? 2 : wide ? kWideCpl : kF32Cpl; }
 struct GroupMember {

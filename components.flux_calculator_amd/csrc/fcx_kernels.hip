@@ -212,11 +212,11 @@ __device__ __forceinline__ Methods type_methods(const TypeParams &tp) {
   const uint64_t w = *cptr(&tp.m_qsur[0]), b = *cptr(&tp.bias_adds);
   return Methods{{byte_of(w, 0), byte_of(w, 1), byte_of(w, 2)}, byte_of(w, 3), byte_of(w, 4),
                  byte_of(w, 5),  byte_of(w, 6), byte_of(w, 7),  byte_of(b, 0),
-                 FCX_CONST_UNIFORM ? (uint32_t)(b >> 32) : 0u,
-                 FCX_SKIP_STORES ? (uint32_t)(uint8_t)(b >> 8) : 0u};
+                 (uint32_t)(b >> 32),
+                 (uint32_t)(uint8_t)(b >> 8)};
 }
 __device__ __forceinline__ uint32_t type_cmask(const TypeParams &tp) {
-  return FCX_CONST_UNIFORM ? (uint32_t)(*cptr(&tp.bias_adds) >> 32) : 0u;
+  return (uint32_t)(*cptr(&tp.bias_adds) >> 32);
 }
 // An input that may be a wave-uniform value (TypeParams::cmask): c set = the member's bytes are
 // the value, splat from the scalar registers, no vector load.  Lanes at or past n get 1 like
@@ -255,16 +255,8 @@ constexpr bool uniform_inputs() {
 __device__ __forceinline__ bool cbit(uint32_t m, int bit) { return (m >> bit) & 1u; }
 // The wait of the single-type kernels for a type's inputs: vmcnt(0) alone (expcnt and lgkmcnt
 // left at their maxima), as a builtin so that the compiler's wait-count pass sees it.
-__device__ __forceinline__ void wait_inputs() {
-#if FCX_INPUT_WAIT
-  __builtin_amdgcn_s_waitcnt(0x0F70);
-#endif
-}
+__device__ __forceinline__ void wait_inputs() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
-// process()'s `early` hook when the caller has nothing to issue behind the inputs' wait
-struct NoEarly {
-  __device__ __forceinline__ void operator()() const {}
-};
 // Momentum of one (type, u- or v-grid) cell group; `north` selects VMOM.
 struct NoEmit {
   template <int C, class R>
@@ -414,30 +406,17 @@ struct RecEmit {
   int P;              // elements per record
   uint64_t posw;      // Params::rec_pos (wave-uniform) as one word, position k in byte k
   int nv;             // cells of the lane inside the grid
-#ifndef FCX_REC_VEC  // 1: the values stay in registers and each record goes out as 16-B stores
-#define FCX_REC_VEC 1
-#endif
-  mutable R vals[6][C];
+  mutable R vals[6][C];  // the values stay in registers and each record goes out as 16-B stores
   __device__ __forceinline__ int pos(int k) const { return byte_of(posw, k); }
   template <int CC, class RR>
   __device__ __forceinline__ void operator()(int k, const Vec<CC, RR> &x) const {
     inner(k, x);
-    if (FCX_REC_VEC) {
-      if (k < 6) {
+    if (k < 6) {
 #pragma unroll
-        for (int i = 0; i < CC; ++i) vals[k][i] = x.v[i];
-      }
-      return;
-    }
-    const int p = pos(k);
-    if (p >= 0) {
-#pragma unroll
-      for (int i = 0; i < CC; ++i)
-        if (i < nv) gptr(rec)[i * P + p] = x.v[i];
+      for (int i = 0; i < CC; ++i) vals[k][i] = x.v[i];
     }
   }
   __device__ __forceinline__ void flush() const {
-    if (!FCX_REC_VEC) return;
     constexpr int V = 16 / sizeof(R);
 #pragma unroll
     for (int i = 0; i < C; ++i) {
@@ -473,25 +452,23 @@ struct RecEmit {
 // precision has it, with and without the fused accumulation.
 // HALO: cells at or past st_end are a halo tile's head cells -- their fluxes are computed for
 // the fused accumulation's products, nothing of them is stored (the next tile's wave stores).
-// early: called once the t-grid inputs of a single-type kernel have landed (TM = 1, after
-// wait_inputs): loads of the caller that depend on values requested with the inputs.
 // PR: the precision (double, float or F32Wide): R its arithmetic and S its storage type.  The
 // inputs are held in S and widened where a formula takes them (the formulas are called as
 // f<R>(...), so a float argument converts on the way in); what the pass computes is held in R.
 template <int C, bool MERGED, int VAR, bool NT, class PR = double, int TM = 1, bool RAVG = false,
-          class Emit = NoEmit, bool REC = false, bool HALO = false, class Early = NoEarly>
+          class Emit = NoEmit, bool REC = false, bool HALO = false>
 __device__ __forceinline__ void process(const Params *__restrict__ P, const double *__restrict__ corr_m,
                                         int64_t j0, const Emit &emit_in = Emit(),
                                         AccLds<C, typename Prec<PR>::arith> acc_lds =
                                             AccLds<C, typename Prec<PR>::arith>{nullptr, 0},
-                                        int64_t st_end = 0, const Early &early = Early()) {
+                                        int64_t st_end = 0) {
   using R = typename Prec<PR>::arith;
   using S = typename Prec<PR>::store;
   constexpr bool kCr = is_cr<PR>();  // the transcendental sites: correctly rounded
   static_assert(!(RAVG && TM), "register averages need more than one surface type");
   static_assert(!REC || (TM == 1 && !RAVG), "remap records: the T=1 launch");
   static_assert(!REC || std::is_same<R, S>::value, "remap records: the fp64 engine");
-  static_assert(!HALO || (TM == 1 && !RAVG) || (FCX_HALO_RAVG && RAVG), "halo tiles: the T=1 launch");
+  static_assert(!HALO || (TM == 1 && !RAVG), "halo tiles: the T=1 launch");
   const uint32_t stages = P->stages;
   const int T = TM ? 1 : P->num_types;
   const int64_t nt = P->n[0];
@@ -569,10 +546,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
   // SIMD, no spills.  In one process over the same arrays (profiles/r03/ab_t2_prefetch.json,
   // random map): T = 2 step 1.672 -> 1.625 ms, CCLM 5.14 -> 5.26 TB/s, MOM5 5.54 -> 5.67,
   // RCO 5.26 -> 5.50.
-#ifndef FCX_T2_PREFETCH  // A/B builds: 0 = no next-type prefetch (24 fewer VGPRs)
-#define FCX_T2_PREFETCH 1
-#endif
-  constexpr bool kPrefetch = kReload && FCX_T2_PREFETCH;
+  constexpr bool kPrefetch = kReload;
   // Multi-type CCLM / MOM5 kernels: the atmosphere-only terms of the formulas are formed once
   // per cell, when the type's atmosphere fields are (re)loaded, instead of once per type:
   // T_a * EF (HSEN's pow, ta_exner) and, for CCLM, whose coefficients AMOI / AMOM are
@@ -719,10 +693,7 @@ __device__ __forceinline__ void process(const Params *__restrict__ P, const doub
       // blocks before it as well.  One wait here, in code that dominates every flux block of
       // the type, and the blocks need none: the stores issue with the arithmetic.  (TM = 0
       // keeps the compiler's waits: a full wait here would also retire the next-type prefetch.)
-      if constexpr (TM == 1) {
-        wait_inputs();
-        early();
-      }
+      if constexpr (TM == 1) wait_inputs();
       // ---- calc_flux_radiation_blackbody (calc:331-343)
       // (every flux block below: run when its output is stored OR wanted though not stored --
       // WantBit --, and only the store is guarded by the pointer)
@@ -951,13 +922,10 @@ constexpr int xrows_doubles(int xrows = kFusedFields) { return xrows * tile_cell
 // segments sits behind the weights row: per segment its first cell and length - 1 (one byte
 // each: a tile has 256 cells) and its atmosphere cell, room for one segment per cell (6 B x
 // 256 = 192 doubles).  16 waves per CU then hold 156 KiB of LDS.
-#ifndef FCX_F32_SEG_ORDINAL
-#define FCX_F32_SEG_ORDINAL 1
-#endif
 constexpr int kSegCap = 192;  // doubles of the list (tile_cells<4>() x (2 + 4) bytes)
 // (S: the storage type -- the rows hold what the arrays hold)
 template <class S, int C>
-constexpr bool seg_ordinal() { return FCX_F32_SEG_ORDINAL && sizeof(S) == 4 && C == 4; }
+constexpr bool seg_ordinal() { return sizeof(S) == 4 && C == 4; }
 // float rows: the doubles in front of the wide kernels' accumulator region (rows, weights, list)
 template <class PR, int C, bool RAVG>
 constexpr int acc_region_doubles() {
@@ -993,7 +961,7 @@ struct LdsEmitT {
       *reinterpret_cast<f4 *>(reinterpret_cast<float *>(p) + k * tile_cells<C>() + C * lane) =
           f4{(float)x.v[0], (float)x.v[1], (float)x.v[2], (float)x.v[3]};
       return;
-    } else if constexpr (sizeof(S) == 4 && C == 2) {  // (kF32Cpl 2: one 8-B store)
+    } else if constexpr (sizeof(S) == 4 && C == 2) {  // (the wide kernels' two cells: one 8-B store)
       const int lane = threadIdx.x & 63;
       *reinterpret_cast<f2v *>(reinterpret_cast<float *>(p) + k * tile_cells<C>() + C * lane) =
           f2v{(float)x.v[0], (float)x.v[1]};
@@ -1020,7 +988,7 @@ __device__ __forceinline__ int first_bit(uint64_t m) { return m ? __builtin_ctzl
 // XCD b % 8), each XCD with its own L2.  Neighbouring tiles share the 128-B lines of the
 // atmosphere outputs their segments end in; mapped to the same XCD, the two partial lines
 // merge in that L2 before write-back instead of reaching memory as two partial writes.
-// XCD runs (round 3): XCD x takes runs of FCX_XCD_CHUNK = 64 consecutive workgroups (256
+// XCD runs (round 3): XCD x takes runs of kXcdChunk = 64 consecutive workgroups (256
 // tiles), the 8 XCDs' runs side by side, so that only one tile edge in 256 is shared between
 // two XCDs AND the chip streams from one window of the arrays, as the dispatch order
 // advances.  Rounds 1-2 gave each XCD one contiguous eighth of the grid, b -> x * (nb / 8) +
@@ -1028,14 +996,12 @@ __device__ __forceinline__ int first_bit(uint64_t m) { return m ? __builtin_ctzl
 // same arrays, runs against eighths (profiles/r03/xcd_map_ab/): step -2.4 / -6.1 % fp64 (two
 // boxes), -2.7 / -2.2 % fp32, -3.1 / -0.8 % at T = 2, -5.4 % on the periodic map.
 constexpr uint32_t kXcds = 8;
-#ifndef FCX_XCD_CHUNK  // workgroups per XCD run (fp64 kernels, 128-cell tiles)
-#define FCX_XCD_CHUNK 64
-#endif
-#ifndef FCX_XCD_CHUNK_F32  // ... and of the fp32 kernels (256-cell tiles): 16 against 64,
-#define FCX_XCD_CHUNK_F32 32  // step -0.7 % (shared arrays) / -4.0 % (own mirrors),
-#endif                        // profiles/r03/xcd_map_ab/f32_*; round 5, the fp32 group launch:
-                              // 32 against 16 -1.0 / -1.2 % (two boxes), 64 -0.2 %, and with
-                              // the ordinal segment rounds -2.1 % (profiles/r05/ord/)
+constexpr uint32_t kXcdChunk = 64;  // workgroups per XCD run (fp64 kernels, 128-cell tiles)
+// ... and of the fp32 kernels (256-cell tiles): 16 against 64, step -0.7 % (shared arrays) /
+// -4.0 % (own mirrors), profiles/r03/xcd_map_ab/f32_*; round 5, the fp32 group launch: 32 against
+// 16 -1.0 / -1.2 % (two boxes), 64 -0.2 %, and with the ordinal segment rounds -2.1 %
+// (profiles/r05/ord/)
+constexpr uint32_t kXcdChunkF32 = 32;
 template <uint32_t K>
 __device__ __forceinline__ uint32_t xcd_block(uint32_t b, uint32_t nb) {
   constexpr uint32_t row = K * kXcds;  // runs of K workgroups per XCD, the XCDs side by side
@@ -1125,30 +1091,21 @@ __device__ __forceinline__ void record_round(const AtmosFused &af, int32_t a, co
 // for the held atmosphere-side inputs (4 -> <= 128 spills them: T = 2 step +24 %).  2 gives
 // the same 3 waves per SIMD (+1 VGPR): -0.7 % in one process over shared arrays, +0.5 % in
 // alternating bench processes on one box (profiles/r03/ravg_blocks_ab/): 3 stays.
-#ifndef FCX_RAVG_ATMOS_BLOCKS
-#define FCX_RAVG_ATMOS_BLOCKS 3
-#endif
+constexpr int kRavgAtmosBlocks = 3;
 // blocks per CU the T=1 fused kernels are compiled for (1: no register cap)
-#ifndef FCX_T1_ATMOS_BLOCKS
-#define FCX_T1_ATMOS_BLOCKS 1
-#endif
+constexpr int kT1AtmosBlocks = 1;
 // ... and the fp32 T=1 fused CCLM / MOM5 kernels (4 cells per lane): 4 = at most 128 VGPRs,
 // 4 waves per SIMD, no spills (uncapped they take 132 / 137 VGPRs and 3 waves); in one
 // process over the same arrays (profiles/r03/ab_f32_4waves.json) CCLM 4.81 -> 5.19 TB/s,
 // MOM5 4.73 -> 5.08.  The fp32 RCO kernel (105 VGPRs, 4 waves either way) lost 5 % under the
-// cap and keeps none.  1 (A/B): no cap.
-#ifndef FCX_F32_ATMOS_BLOCKS
-#define FCX_F32_ATMOS_BLOCKS 4
-#endif
-// waves per block of the fused kernel (A/B knobs)
-#ifndef FCX_ATMOS_WAVES
-#define FCX_ATMOS_WAVES 4
-#endif
-#ifndef FCX_F32_ATMOS_WAVES  // A/B: 2 paid while the fp32 rows held fp64 products (13.8 KB/wave)
-#define FCX_F32_ATMOS_WAVES 4
-#endif
+// cap and keeps none.
+constexpr int kF32AtmosBlocks = 4;
+// waves per block of the fused kernel
+constexpr int kAtmosWaves = 4;
+// ... and of the fp32 ones (2 paid while the fp32 rows held fp64 products, 13.8 KB/wave)
+constexpr int kF32AtmosWaves = 4;
 template <int C>
-constexpr int atmos_waves() { return C == 4 ? FCX_F32_ATMOS_WAVES : FCX_ATMOS_WAVES; }
+constexpr int atmos_waves() { return C == 4 ? kF32AtmosWaves : kAtmosWaves; }
 // HALO (T = 1, full-range launches, maps whose segments are at most halo * C + 1 cells): a
 // wave owns the first 64 - halo lanes' cells of its tile and computes the last `halo` lanes'
 // cells -- the head of the next tile -- only for their products (nothing of them is stored),
@@ -1231,20 +1188,15 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
       next_cont = tend < n && gptr(af.idx)[tend] == gptr(af.idx)[tend - 1];
     }
     // kCompact: the atmosphere cells of the lane's segment starts, a load that depends on the
-    // bit word and the prefix count.  FCX_EARLY_SEG_ATM: issued by process() right behind its
-    // wait for the inputs (word and count have landed with them), so that it flies during the
-    // arithmetic and its wait after the flux pass is a counted one, not a drain of the stores.
-    bool a_loaded = false;
+    // bit word and the prefix count, issued after the flux pass (issued right behind the inputs'
+    // wait, in flight during the arithmetic, it measured no gain: DESIGN.md section 3).
+    // Kept as a lambda so that the load sequence is formed ahead of the flux pass.
     auto seg_atm_loads = [&]() {
-      if constexpr (kCompact) {
-        int32_t ord = before + __builtin_popcount(word & ((1u << sh) - 1u));
+      int32_t ord = before + __builtin_popcount(word & ((1u << sh) - 1u));
 #pragma unroll
-        for (int i = 0; i < C; ++i)
-          if (j0 + i < n && ((word >> (sh + i)) & 1u)) a[i] = gptr(af.seg_atm)[ord++];
-        a_loaded = true;
-      }
+      for (int i = 0; i < C; ++i)
+        if (j0 + i < n && ((word >> (sh + i)) & 1u)) a[i] = gptr(af.seg_atm)[ord++];
     };
-    constexpr bool kEarly = kCompact && TM == 1 && FCX_INPUT_WAIT && FCX_EARLY_SEG_ATM;
     if (j0 < n) {
       // the lane's accumulators (RAVG; flux_rows): fp64 rows -- slot k is the lane's entry of
       // product row k; float rows, float arithmetic -- slot k is the lane's entry of flux row k;
@@ -1257,11 +1209,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
         else
           return AccLds<C, R>{wp + acc_region_doubles<PR, C, RAVG>() + C * lane, 64 * C};
       }();
-      if constexpr (kEarly)
-        process<C, true, VAR, NT, PR, TM, RAVG, LdsEmitT<C, S>, REC, (HALO != 0)>(P, corr_m, j0, emit, acc, t0 + kO,
-                                                                                  seg_atm_loads);
-      else
-        process<C, true, VAR, NT, PR, TM, RAVG, LdsEmitT<C, S>, REC, (HALO != 0)>(P, corr_m, j0, emit, acc, t0 + kO);
+      process<C, true, VAR, NT, PR, TM, RAVG, LdsEmitT<C, S>, REC, (HALO != 0)>(P, corr_m, j0, emit, acc, t0 + kO);
     }
     if constexpr (kXF) {  // the weights row of the fp32 fluxes (dead cells: weight 0)
 #pragma unroll
@@ -1286,7 +1234,7 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
     bool st[C];
     uint64_t m[C];
     if constexpr (kCompact) {
-      if (!a_loaded) seg_atm_loads();
+      seg_atm_loads();
 #pragma unroll
       for (int i = 0; i < C; ++i) {
         st[i] = !(j0 + i < n) || ((word >> (sh + i)) & 1u);
@@ -1439,21 +1387,19 @@ __device__ __forceinline__ void atmos_tile(const Params *__restrict__ P, const d
 
 // ... and the wide ones (F32Wide, kWideCpl = 2 cells per lane): 2 = at most 256 VGPRs, which
 // leaves the compiler free -- at two cells per lane they take 79-125 VGPRs, 4 waves or more per
-// SIMD, no scratch (profiles/r13/f32_math/isa/).  At four cells per lane (FCX_WIDE_CPL 4, A/B)
+// SIMD, no scratch (profiles/r13/f32_math/isa/).  At four cells per lane (kWideCpl 4, measured)
 // they took 172-197 and 2 waves, and 20-88 B of scratch under a cap of 3 blocks.
-#ifndef FCX_WIDE_ATMOS_BLOCKS
-#define FCX_WIDE_ATMOS_BLOCKS 2
-#endif
+constexpr int kWideAtmosBlocks = 2;
 template <int C, class R, int VAR, bool NT, int TM, bool RAVG, bool REC = false, int HALO = 0>
 // (REC: the record stores took CCLM to 129 VGPRs and 3 waves per SIMD; capped at 4 blocks = 4 waves)
 // (F64Cr, CCLM and MOM5: 2 as for the wide ones -- the correctly rounded sites of two cells
 // take 241-251 VGPRs left free, and 180-250 B of scratch under the fp64 caps of 3 and 4)
-__global__ __launch_bounds__(64 * atmos_waves<C>(), (is_cr<R>() && VAR != 3) ? FCX_WIDE_ATMOS_BLOCKS
-                                                  : RAVG  ? FCX_RAVG_ATMOS_BLOCKS
+__global__ __launch_bounds__(64 * atmos_waves<C>(), (is_cr<R>() && VAR != 3) ? kWideAtmosBlocks
+                                                  : RAVG  ? kRavgAtmosBlocks
                                                   : REC ? 4
-                                                  : is_wide<R>() ? FCX_WIDE_ATMOS_BLOCKS
-                                                  : (C == 4 && VAR != 3) ? FCX_F32_ATMOS_BLOCKS
-                                                                         : FCX_T1_ATMOS_BLOCKS) void cells_atmos_kernel(const Params *__restrict__ P,
+                                                  : is_wide<R>() ? kWideAtmosBlocks
+                                                  : (C == 4 && VAR != 3) ? kF32AtmosBlocks
+                                                                         : kT1AtmosBlocks) void cells_atmos_kernel(const Params *__restrict__ P,
                                                           const double *__restrict__ corr_m,
                                                           const AtmosFused af, int64_t lo, int64_t hi) {
   using S = typename Prec<R>::store;  // (R: the precision -- double, float or F32Wide)
@@ -1462,9 +1408,9 @@ __global__ __launch_bounds__(64 * atmos_waves<C>(), (is_cr<R>() && VAR != 3) ? F
   // the type-0 averages (slot k = row k, TSUR in an extra row), then hold w * average
   // (float rows: the averages themselves; their accumulators: flux_rows)
   __shared__ double s_p[atmos_waves<C>()][wave_lds_doubles<R, C, RAVG>()];
-  static_assert(!RAVG || lds_fits<R, C, RAVG>(FCX_RAVG_ATMOS_BLOCKS, atmos_waves<C>()),
+  static_assert(!RAVG || lds_fits<R, C, RAVG>(kRavgAtmosBlocks, atmos_waves<C>()),
                 "register averages: the launch bound's blocks per CU hold at most 160 KiB of LDS");
-  static_assert(!HALO || (TM == 1 && !RAVG) || (FCX_HALO_RAVG && RAVG), "halo tiles: the T=1 launch");
+  static_assert(!HALO || (TM == 1 && !RAVG), "halo tiles: the T=1 launch");
   const int own_lanes = HALO ? 64 - af.halo : 64;
   const int64_t kO = (int64_t)C * own_lanes;  // cells a tile owns (HALO: lo == 0)
   const int64_t n_tiles = af.n_tiles;  // (hi + kO - 1) / kO, from the host
@@ -1472,7 +1418,7 @@ __global__ __launch_bounds__(64 * atmos_waves<C>(), (is_cr<R>() && VAR != 3) ? F
   double *wp = s_p[wv];
   const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
   const int64_t wave0 =
-      (int64_t)xcd_block<C == 4 ? FCX_XCD_CHUNK_F32 : FCX_XCD_CHUNK>(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + wv;
+      (int64_t)xcd_block<C == 4 ? kXcdChunkF32 : kXcdChunk>(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + wv;
 #if FCX_WAVE_TRACE
   const int lane = threadIdx.x & 63;
   const uint64_t trace_start = (uint64_t)wall_clock64();
@@ -1509,15 +1455,13 @@ __global__ __launch_bounds__(64 * atmos_waves<C>(), (is_cr<R>() && VAR != 3) ? F
 // Blocks per CU the fp64 T = 1 group kernel is compiled for: 4 = 128 VGPRs, 4 waves per SIMD
 // like the members' own kernels (left free, the three inlined bodies take 139-146 VGPRs and
 // 3 waves; at 128 one 8-B value of the preamble spills: one store and two reloads per wave).
-// The multi-type group (RAVG) keeps the members' FCX_RAVG_ATMOS_BLOCKS, in every precision.
-#ifndef FCX_GROUP_BLOCKS
-#define FCX_GROUP_BLOCKS 4
-#endif
+// The multi-type group (RAVG) keeps the members' kRavgAtmosBlocks, in every precision.
+constexpr int kGroupBlocks = 4;
 template <int C, class R, bool NT, int HALO, int TM = 1, bool RAVG = false>
-__global__ __launch_bounds__(64 * atmos_waves<C>(), is_cr<R>() ? FCX_WIDE_ATMOS_BLOCKS
-                                                    : RAVG ? FCX_RAVG_ATMOS_BLOCKS
-                                                    : is_wide<R>() ? FCX_WIDE_ATMOS_BLOCKS
-                                                    : C == 4 ? FCX_F32_ATMOS_BLOCKS : FCX_GROUP_BLOCKS) void
+__global__ __launch_bounds__(64 * atmos_waves<C>(), is_cr<R>() ? kWideAtmosBlocks
+                                                    : RAVG ? kRavgAtmosBlocks
+                                                    : is_wide<R>() ? kWideAtmosBlocks
+                                                    : C == 4 ? kF32AtmosBlocks : kGroupBlocks) void
 cells_atmos_group_kernel(const GroupArgs g, const Params *__restrict__ P0, const Params *__restrict__ P1,
                          const Params *__restrict__ P2, const Params *__restrict__ P3) {
   // The members' parameter blocks are separate const __restrict__ kernel arguments (not the
@@ -1527,13 +1471,13 @@ cells_atmos_group_kernel(const GroupArgs g, const Params *__restrict__ P0, const
   // round trip before the field loads): the group kernel took 1.156 ms against 0.783 ms
   // for the three launches it replaced (a round-4 diagnostic build, not kept).
   __shared__ double s_p[atmos_waves<C>()][wave_lds_doubles<R, C, RAVG>()];
-  static_assert(!RAVG || lds_fits<R, C, RAVG>(FCX_RAVG_ATMOS_BLOCKS, atmos_waves<C>()),
+  static_assert(!RAVG || lds_fits<R, C, RAVG>(kRavgAtmosBlocks, atmos_waves<C>()),
                 "register averages: the launch bound's blocks per CU hold at most 160 KiB of LDS");
   const int wv = threadIdx.x >> 6;
   double *wp = s_p[wv];
   const int64_t waves = (int64_t)gridDim.x * (blockDim.x >> 6);
   const int64_t wave0 =
-      (int64_t)xcd_block<C == 4 ? FCX_XCD_CHUNK_F32 : FCX_XCD_CHUNK>(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + wv;
+      (int64_t)xcd_block<C == 4 ? kXcdChunkF32 : kXcdChunk>(blockIdx.x, gridDim.x) * (blockDim.x >> 6) + wv;
   for (int64_t t = wave0; t < g.total_tiles; t += waves) {
     // the range and member of tile t: wave-uniform, said so to the compiler (readfirstlane),
     // so that their parameters are scalar loads -- derived from threadIdx.x >> 6, the index
@@ -1645,10 +1589,7 @@ __global__ __launch_bounds__(256) void regrid_csr_kernel(const int32_t *__restri
 // products w*x per field, then every lane adds the products of its own segment in link
 // order.  acc = acc + w*x from 0.0 in increasing link order is exactly the sequential
 // weight application, so the result is bit-identical to it (no atomics, no tree order).
-#ifndef FCX_ATM_CHUNK
-#define FCX_ATM_CHUNK 512
-#endif
-constexpr int kAtmChunk = FCX_ATM_CHUNK;
+constexpr int kAtmChunk = 512;
 
 // R: element type of the fields and outputs (float in the fp32 engine; the weights, the
 // products and the sums are fp64 either way, and an fp32 output is rounded once).
@@ -1902,7 +1843,7 @@ __global__ __launch_bounds__(256) void receive_inject_kernel(const ReceiveArgs a
         }
         o.v[i] = (R)acc;
       }
-      st<C, FCX_RECV_NT != 0, R>(reinterpret_cast<R *>(a.dst[f]) + shift, j0, a.n, o);
+      st<C, false, R>(reinterpret_cast<R *>(a.dst[f]) + shift, j0, a.n, o);
     }
   }
 }
@@ -2042,13 +1983,7 @@ static int launch_atm_f64(const Params *hp, const LaunchConfig &lc, int blocks, 
       launch_atm<2, PR, VAR, 1, false, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
     else
       launch_atm<2, PR, VAR, 1, false>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
-  } else if (lc.ravg) {
-    if constexpr (FCX_HALO_RAVG) {
-      if (halo) {
-        launch_atm<2, PR, VAR, 0, true, false, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
-        return 0;
-      }
-    }
+  } else if (lc.ravg) {  // (crossing records: halo tiles are the T = 1 launches')
     launch_atm<2, PR, VAR, 0, true>(lc.nontemporal, blocks, s, dp, corr_m, af, lo, hi);
   } else
     return (int)hipErrorInvalidValue;
@@ -2063,7 +1998,7 @@ template <int VAR>
 static int launch_atm_r(const Params *hp, const LaunchConfig &lc, int blocks, hipStream_t s, const Params *dp,
                         const double *corr_m, const AtmosFused &af, int64_t lo, int64_t hi) {
   const bool halo = lc.halo > 0;
-  if (halo && ((hp->num_types != 1 && !(FCX_HALO_RAVG && lc.ravg)) || lo != 0)) return (int)hipErrorInvalidValue;
+  if (halo && (hp->num_types != 1 || lo != 0)) return (int)hipErrorInvalidValue;
   if (lc.wide && !lc.f32) return (int)hipErrorInvalidValue;
   if (lc.cr && lc.f32) return (int)hipErrorInvalidValue;
   if (lc.cr) return launch_cr_fused(VAR, hp, lc, blocks, s, dp, corr_m, af, lo, hi);

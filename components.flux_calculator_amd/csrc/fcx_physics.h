@@ -4,7 +4,8 @@
 // uses -r8, build_hlrnb.sh:26, so `17.2693882` is a REAL(8) constant) and every expression
 // keeps the Fortran left-to-right evaluation order.  The translation unit is compiled
 // with -ffp-contract=off so no FMA is formed: in double the results differ from the
-// reference only through the last-ulp behaviour of exp/pow (ROCm ocml vs glibc).
+// reference only through the last-ulp behaviour of exp/pow (ROCm ocml vs glibc).  The one power,
+// the Exner ratio's, is exp(y * log x) (pow_exner: why it is as close as a library pow).
 //
 // R is the arithmetic type: double (the reference semantics) or float (the fp32 variant of
 // fp32 storage and arithmetic, constants folded in double and then
@@ -112,20 +113,13 @@ __device__ __forceinline__ R meva_rco(R qa, R ts, R vel) {
 // to x**y as a library pow (last-ulp differences only, like the reference's own pow against
 // ROCm's), at a fraction of ROCm's fp64 pow, which carries extra-precision log/exp for any
 // base.  Special values agree with pow for y > 0 (0 -> 0, inf -> inf, x < 0 or NaN -> NaN).
-#ifndef FCX_POW_EXPLOG
-#define FCX_POW_EXPLOG 1
-#endif
 template <class R, bool CR = false>
 __device__ __forceinline__ R pow_exner(R x, R y) {
   if constexpr (CR) {
     static_assert(std::is_same<R, double>::value, "correctly rounded sites: the fp64 engine");
     return cr_pow_exner(x, y);
   }
-#if FCX_POW_EXPLOG
   return exp(y * log(x));
-#else
-  return pow(x, y);
-#endif
 }
 
 // flux_lib/heat/flux_heat_sensible.F90:74-94 (flux_heat_sensible_cclm; _mom5 = with CHEA).

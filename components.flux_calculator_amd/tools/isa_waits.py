@@ -6,6 +6,10 @@
   python tools/isa_waits.py --compile [-D...] [filter]   csrc/fcx_kernels.hip compiled to assembly
                                                      with the Makefile's flags (plus any -D given)
   python tools/isa_waits.py --asm FILE.s [filter]    an assembly file from such a compile
+  python tools/isa_waits.py --same LIB_A LIB_B       two builds compared instruction for instruction:
+                                                     the kernels only in one, the kernels that differ
+                                                     with their first differing line; exit status 1
+                                                     unless the two hold the same code
 
 Per kernel: the instructions, the sub-dword vector loads (a byte or short member of the
 parameter block read through the vector-memory pipeline: a round trip and a wait, where an
@@ -138,7 +142,45 @@ def report(funcs, flt=""):
     return rows
 
 
+def same(funcs_a, funcs_b):
+    """two {kernel: [instructions]} compared: (names only in A, names only in B, {name of a kernel
+    whose lists differ: (index, instruction of A, instruction of B) of the first differing line,
+    None standing for the end of the shorter list})"""
+    only_a = sorted(set(funcs_a) - set(funcs_b))
+    only_b = sorted(set(funcs_b) - set(funcs_a))
+    differ = {}
+    for name in sorted(set(funcs_a) & set(funcs_b)):
+        a, b = funcs_a[name], funcs_b[name]
+        if a == b:
+            continue
+        i = next((k for k, (x, y) in enumerate(zip(a, b)) if x != y), min(len(a), len(b)))
+        differ[name] = (i, a[i] if i < len(a) else None, b[i] if i < len(b) else None)
+    return only_a, only_b, differ
+
+
+def main_same(lib_a, lib_b):
+    fa, fb = disassemble(lib_a), disassemble(lib_b)
+    only_a, only_b, differ = same(fa, fb)
+    names = demangle(sorted(set(fa) | set(fb)))
+    print(f"A: {lib_a}: {len(fa)} functions, {sum(map(len, fa.values()))} instructions")
+    print(f"B: {lib_b}: {len(fb)} functions, {sum(map(len, fb.values()))} instructions")
+    for title, only in (("only in A", only_a), ("only in B", only_b)):
+        print(f"{title}: {len(only)}")
+        for n in only:
+            print(f"    {names[n]}")
+    print(f"differ: {len(differ)}")
+    for n, (i, x, y) in differ.items():
+        print(f"    {names[n]}\n        instruction {i}: A: {x}\n        {'':>{len(str(i)) + 13}}B: {y}")
+    ok = not (only_a or only_b or differ)
+    print("same: " + ("yes" if ok else "NO"))
+    return 0 if ok else 1
+
+
 def main(argv):
+    if argv and argv[0] == "--same":
+        if len(argv) != 3:
+            sys.exit("usage: isa_waits.py --same LIB_A LIB_B")
+        sys.exit(main_same(argv[1], argv[2]))
     args, defines, src = list(argv), [], ("lib", os.path.join(PKG, "lib", "libfcx.so"))
     flt = ""
     while args:

@@ -3,7 +3,7 @@ between the arrays, so that a store past an output, a load past an input or a wr
 input shows up (tests/test_guards.py on the CPU, tests/test_gpu_guard_bands.py on the GPU).
 
   * The band on each side of every array is at least BAND = two layout tiles
-    (2 << FCX_LAYOUT_SHIFT = 8192 elements): wider than any block tile, chunk or grid-length
+    (2 << kLayoutShift = 8192 elements): wider than any block tile, chunk or grid-length
     difference the tests use, so every access a correct or an incorrect tail can make stays
     inside the arena's own allocation; a longer overrun lands in the next array, where the
     parity or the input check sees it.
@@ -23,7 +23,7 @@ import itertools
 
 import numpy as np
 
-LAYOUT_SHIFT = 12  # FCX_LAYOUT_SHIFT: the engine's mirrors are cut into tiles of 4096 cells
+LAYOUT_SHIFT = 12  # kLayoutShift (fcx_internal.h): the engine's mirrors are cut into tiles of 4096 cells
 BAND = 2 << LAYOUT_SHIFT
 _SLACK = 4  # elements an array start may move to reach its offset modulo 16 bytes
 
